@@ -9,6 +9,11 @@ per-GPU work is constant; 8 GPUs = 8M leaves x 30k sites.  One step = post-order
 pre-order + mutation assignment + per-site score over the rank's shard, then one RCCL
 all-gather of (score, root code) per site.  Inputs are generated on the
 device before timing (resident in HBM).
+
+A plain run sets up, warms up, times `--steps` steps and prints the headline line
+(`--dump-outputs DIR` also writes the last step's results).  `--full` adds what takes runs
+of its own: the per-kernel roofline, the CPU baselines and parity samples, and the `--with`
+blocks (Sankoff and C5 replay lines, end-to-end rate, command-level wall times).
 """
 from __future__ import annotations
 
@@ -28,7 +33,8 @@ sys.path.insert(0, ROOT)
 import panman_amd  # noqa: E402  (after torch: one HIP runtime per process)
 from panman_amd.shard import gather_site_results_device, shard_range  # noqa: E402
 
-HBM_PEAK_GBS = 8000.0   # MI355X spec (MI355X_MICROARCH.md chip-level table)
+FULL_ENV = "PANMAN_BENCH_FULL"   # "1": --full without naming it on the command line
+HBM_PEAK_GBS = 8000.0  # MI355X spec (MI355X_MICROARCH.md chip-level table)
 
 
 def parse():
@@ -36,14 +42,23 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=5)
     p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--full", action="store_true", default=os.environ.get(FULL_ENV, "0") not in ("", "0"),
+                   help="beside the headline figure: the per-kernel roofline (an untimed eager pass, the "
+                        "measured copy / write rates), the CPU baseline and parity sample, and the --with "
+                        "blocks.  Without it a run sets up, warms up, times the steps and prints the line.  "
+                        f"Off by default; {FULL_ENV}=1 in the environment turns it on (the tools/ scripts "
+                        "that read the full line export it)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last step computed as DIR/<name>.npy "
+                        "(float32 / float64; a seeded sample of the large arrays)")
     p.add_argument("--leaves", type=int, default=1_000_000, help="leaves per GPU")
     p.add_argument("--sites", type=int, default=30_000, help="alignment columns in total")
     p.add_argument("--cpu-sites", type=int, default=0,
                    help="columns timed on the all-core CPU baseline (0: 2 per host thread, at least 512)")
     p.add_argument("--cpu-threads", type=int, default=0, help="CPU baseline threads (0: every core this process may use)")
-    p.add_argument("--no-cpu", action="store_true")
+    p.add_argument("--no-cpu", action="store_true", help="--full without the CPU baselines")
     p.add_argument("--e2e", action="store_true",
-                   help="also time the end-to-end path (H2D of the packed leaf matrix, the run, D2H of "
+                   help="(--full) also time the end-to-end path (H2D of the packed leaf matrix, the run, D2H of "
                         "every mutation record) on the same workload (SURVEY.md §8d), N=1 only")
     p.add_argument("--cpu-sites-1t", type=int, default=4, help="columns timed on the 1-thread CPU baseline")
     p.add_argument("--eager", action="store_true",
@@ -84,13 +99,15 @@ def parse():
     p.add_argument("--replay-block-len", type=int, default=10_000)
     p.add_argument("--cpu-leaves", type=int, default=128, help="leaves replayed on the CPU baseline (~10 s)")
     p.add_argument("--with", dest="with_", default="sankoff,replay,e2e,commands",
-                   help="secondary blocks in the default run's line: comma list of sankoff (N* Sankoff "
+                   help="secondary blocks in a --full run's line: comma list of sankoff (N* Sankoff "
                         "line), replay (C5 FASTA replay line), e2e (PCIe-inclusive rate), commands "
                         "(panmanUtils -M / --low-mem-mode / -I --fasta-aligned wall times beside the "
                         "oracle's restated drivers), or none")
     p.add_argument("--traffic", default=os.path.join(ROOT, "profiles", "traffic_fitch.json"),
                    help="PMC-derived HBM bytes per launch (written by tools/pmc_traffic.py)")
     a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
     a.graph = not a.eager
     return a
 
@@ -112,7 +129,7 @@ def main():
     torch.cuda.set_device(local)
     if world > 1:
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
-    extra = set() if args.with_ == "none" else set(args.with_.split(","))
+    extra = set() if args.with_ == "none" or not args.full else set(args.with_.split(","))
 
     L = args.leaves * world
     S = args.sites
@@ -172,7 +189,7 @@ def main():
                lib_gather=gather.startswith("pm_run_gather"))
 
     mode = panman_amd.MODE_FITCH if args.mode == "fitch" else panman_amd.MODE_SANKOFF
-    main_block = parsimony_block(args, eng, mode, ctx)
+    main_block = parsimony_block(args, eng, mode, ctx, dump=args.dump_outputs)
     footprint = {"fitch" if mode == panman_amd.MODE_FITCH else "sankoff": eng.memory_footprint()}
     secondary = {}
     if mode == panman_amd.MODE_FITCH and "sankoff" in extra:
@@ -184,11 +201,11 @@ def main():
 
     cpu = None
     parity = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         log(rank, f"[bench] CPU baseline ({time.time() - t0:.1f}s)")
         cpu, parity = cpu_baseline(args, eng, off, idx, root, L, n_nodes, mode)
     e2e = None
-    if rank == 0 and world == 1 and (args.e2e or "e2e" in extra):
+    if rank == 0 and world == 1 and args.full and (args.e2e or "e2e" in extra):
         log(rank, f"[bench] end to end ({time.time() - t0:.1f}s)")
         e2e = end_to_end(eng, L, S, n_nodes, mode)
     eng.close()
@@ -246,6 +263,12 @@ def main():
                               if kk in v}
                           for k, v in secondary.items()} or None,
         }
+        if not args.full:   # the headline figure only
+            for k in ("roofline", "upload", "footprint", "cpu_baseline", "parity_sample", "end_to_end",
+                      "commands", "secondary"):
+                del out[k]
+        if args.dump_outputs:
+            out["outputs"] = main_block["outputs"]
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
@@ -274,9 +297,10 @@ def workload_label(mode: str, tree: str, L: int, S: int, world: int) -> str:
     return f"{mode}: {shape} (not a BASELINE config size)"
 
 
-def parsimony_block(args, eng, mode, ctx):
+def parsimony_block(args, eng, mode, ctx, dump=None):
     """Warm up, time exactly `steps` steps of `mode` (barrier + synchronize on both sides,
-    max over ranks), then the per-kernel roofline of the dominant kernel."""
+    max over ranks), write the last step's results under `dump` if given, then (--full) the
+    per-kernel roofline of the dominant kernel."""
     world, rank, L, S, s_local, n_nodes = (ctx[k] for k in ("world", "rank", "L", "S", "s_local", "n_nodes"))
     # per-site (score, root code) of every site of the job, on every rank
     score_all = torch.zeros(S, dtype=torch.int32, device="cuda")
@@ -313,19 +337,22 @@ def parsimony_block(args, eng, mode, ctx):
     elapsed = time.perf_counter() - t_start
     if world == 1:   # untimed: the last step's (score, root code), record buffers checked
         eng.site_results_device(score_all.data_ptr(), root_all.data_ptr())
-    if args.graph:   # per-kernel durations for the roofline: same steps, eager, untimed
+    outputs = dump_parsimony(dump, eng, score_all, root_all) if dump and rank == 0 else None
+    if args.full and args.graph:   # per-kernel durations for the roofline: same steps, eager, untimed
         eng.set_graph(False)
         eng.set_profiling(True)
         for _ in range(args.steps):
             eng.run(mode)
         torch.cuda.synchronize()
-    ms, launches = eng.kernel_times(6)
-    # the pre-order pass = its levels / sweeps (class 1) + its tail launch (class 5)
-    tail_ms, tail_launches = ms[5], launches[5]
-    ms[1] += tail_ms
-    launches[1] += tail_launches
+    if args.full:
+        ms, launches = eng.kernel_times(6)
+        # the pre-order pass = its levels / sweeps (class 1) + its tail launch (class 5)
+        tail_ms, tail_launches = ms[5], launches[5]
+        ms[1] += tail_ms
+        launches[1] += tail_launches
     eng.set_profiling(False)
-    design = eng.design_bytes()   # counted from the last run's record masks (untimed)
+    if args.full:
+        design = eng.design_bytes()   # counted from the last run's record masks (untimed)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -339,12 +366,54 @@ def parsimony_block(args, eng, mode, ctx):
     updates = float(S) * n_nodes * args.steps
     value = updates / elapsed
     ms_step = elapsed * 1e3 / args.steps
-    roofline = roofline_of(args, mode, ms, launches, design, ctx, muts, ms_step, rank, tail_ms, tail_launches)
+    roofline = roofline_of(args, mode, ms, launches, design, ctx, muts, ms_step, rank, tail_ms, tail_launches) \
+        if args.full else None
     name = "fitch" if mode == panman_amd.MODE_FITCH else "sankoff"
     return {"metric": f"Fitch-Sankoff site*node updates/sec ({name} mode)", "value": value,
             "unit": "site*node updates/s", "ms_per_step": ms_step, "mutations_total": muts_total,
-            "roofline": roofline,
+            "roofline": roofline, "outputs": outputs,
             "config": {"workload": workload_label(name, args.tree, L, S, world), "sites_per_gpu": s_local}}
+
+
+DUMP_ROWS = 1 << 20   # rows (or bytes of text) kept of an output too large to write whole
+DUMP_SEED = 7
+
+
+def sample_rows(n: int) -> np.ndarray:
+    """Row indices of the --dump-outputs sample, ascending: every row up to DUMP_ROWS, else a
+    seeded draw that depends on n alone (so two builds with equal outputs write equal files)."""
+    if n <= DUMP_ROWS:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_ROWS))
+
+
+def write_outputs(dirname: str, arrays: dict) -> dict:
+    """DIR/<name>.npy for each array; returns {name: shape} for the result line."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
+def dump_parsimony(dirname, eng, score_all, root_all):
+    """--dump-outputs: what a caller holds after the last timed step -- every site's (score,
+    root code), and this rank's mutation records (node, site, type, code) in (node, site)
+    order: their number, and a seeded sample of the rows (N* has 1.3e8 of them; the records
+    come through pm_mutations_fetch, the one way a caller receives them).  Every array is cut
+    to DUMP_ROWS rows, so the files stay under 48 MB whatever the shape."""
+    recs = eng.mutations_raw()
+    raw = recs[sample_rows(recs.shape[0])]
+    sites = sample_rows(score_all.shape[0])
+    muts = np.empty((raw.shape[0], 4), np.float64)
+    muts[:, 0] = raw[:, 0]
+    muts[:, 1] = raw[:, 1] >> 8
+    muts[:, 2] = (raw[:, 1] >> 4) & 15
+    muts[:, 3] = raw[:, 1] & 15
+    return write_outputs(dirname, {
+        "site_score": score_all.cpu().numpy()[sites].astype(np.float64),
+        "site_root_code": root_all.cpu().numpy()[sites].astype(np.float32),
+        "mutation_count": np.array([recs.shape[0]], np.float64),
+        "mutations_sample": muts})
 
 
 def traffic_key(mode: str, tree: str, leaves: int, sites: int) -> str:
@@ -785,17 +854,31 @@ def replay_main(args):
     torch.cuda.set_device(local)
     if world > 1:
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
-    out = replay_block(args, world, rank, local)
+    out = replay_block(args, world, rank, local, dump=args.dump_outputs)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
 
 
-def replay_block(args, world, rank, local):
+def dump_replay(dirname, eng):
+    """--dump-outputs: the aligned FASTA text of the rows the last replay_run left in the
+    context (pm_replay_format) -- its length, and a seeded sample of its bytes (C5's is 5 GB)."""
+    import ctypes as C
+    ptr, n = C.c_void_p(), C.c_int64(0)
+    eng._check(eng.lib.pm_replay_format(eng.ctx, 1, C.byref(ptr), C.byref(n)), "pm_replay_format")
+    try:
+        text = np.ctypeslib.as_array((C.c_uint8 * n.value).from_address(ptr.value))
+        sample = text[sample_rows(n.value)].astype(np.float32)
+    finally:
+        eng.lib.pm_free(ptr)
+    return write_outputs(dirname, {"fasta_bytes": np.array([n.value], np.float64), "fasta_sample": sample})
+
+
+def replay_block(args, world, rank, local, dump=None):
     """FASTA replay (R1-R3) on config C5 (E. coli-like PanMAT, synthetic): leaf*column/s of
-    the GPU replay (consensus expansion + path mutations), inputs resident in HBM; host
-    formatting and the end-to-end rate are reported beside it."""
+    the GPU replay (consensus expansion + path mutations), inputs resident in HBM; with --full
+    host formatting, the end-to-end rate and a CPU baseline are reported beside it."""
     import ctypes as C
 
     from panman_amd.synth import c5_panmat
@@ -844,6 +927,22 @@ def replay_block(args, world, rank, local):
         elapsed = float(t.item())
     units = float(leaves) * cols
     value = float(total_leaves) * cols * args.steps / elapsed
+    outputs = dump_replay(dump, eng) if dump and rank == 0 else None
+    head = {   # the headline figure: the whole line of a plain run, the start of a --full one
+        "metric": "FASTA replay leaf*column/s (aligned, GPU replay kernels)", "build_id": panman_amd.build_id(),
+        "value": value, "unit": "leaf*column/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed * 1e3 / args.steps, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "u8 (ASCII IUPAC)",
+        "data": f"synthetic C5-like PanMAT (seeded: {args.replay_tree} tree, blocks, gap slots, block and nuc mutations)",
+        "config": {"workload": f"C5 replay: {total_leaves} leaves x {cols} aligned columns, "
+                               f"{args.replay_blocks} blocks, {edits} edits, {args.replay_tree} tree",
+                   "kernel": kernel},
+    }
+    if outputs:
+        head["outputs"] = outputs
+    if not args.full:
+        eng.close()
+        return head
     # path mutation records per leaf (8 B each in the SURVEY.md §8d replay model)
     a = pm._arrays
     per_node = np.diff(a["nuc_mut_offsets"])
@@ -921,13 +1020,8 @@ def replay_block(args, world, rank, local):
     # the replay's bytes are ~98 % row writes: the achievable write-only rate beside the spec
     write_gbs = round(panman_amd.stream_write_rate(torch.cuda.current_device()), 1) if rank == 0 else None
     out = {
-        "metric": "FASTA replay leaf*column/s (aligned, GPU replay kernels)", "build_id": panman_amd.build_id(),
-        "value": value, "unit": "leaf*column/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": elapsed * 1e3 / args.steps, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "u8 (ASCII IUPAC)",
-        "data": f"synthetic C5-like PanMAT (seeded: {args.replay_tree} tree, blocks, gap slots, block and nuc mutations)",
-        "config": {"workload": f"C5 replay: {total_leaves} leaves x {cols} aligned columns, "
-                               f"{args.replay_blocks} blocks, {edits} edits, {args.replay_tree} tree",
+        **head,
+        "config": {**head["config"],
                    "leaves": total_leaves, "leaves_per_gpu": leaves, "columns": cols,
                    "path_mutation_records_rank0": path_recs,
                    "parallelism": f"leaf shards x{world}, tree + mutations replicated, no collective"},

@@ -1,4 +1,5 @@
 #!/bin/bash
+export PANMAN_BENCH_FULL=1   # bench.py prints the full report (as with --full): the lines below read it
 # Interleaved A/B of variant libraries on the GPU box:
 #   tools/ab_variants.sh MODE REPS VARIANT...   (VARIANT = default or a build_var/NAME)
 set -o pipefail

@@ -1,4 +1,5 @@
 #!/bin/bash
+export PANMAN_BENCH_FULL=1   # bench.py prints the full report (as with --full): the lines below read it
 # C4 rank share (8M leaves x 3750 sites: one rank of bench.py --gpus 8), by set-record load
 # policy: gpurun_out/c4_share_nt{-1,0,1}.json
 set -o pipefail

@@ -1,4 +1,5 @@
 #!/bin/bash
+export PANMAN_BENCH_FULL=1   # bench.py prints the full report (as with --full): the lines below read it
 # GPU test suite + Fitch/Sankoff bench lines (no CPU baseline)
 set -o pipefail
 mkdir -p gpurun_out

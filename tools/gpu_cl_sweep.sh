@@ -1,4 +1,5 @@
 #!/bin/bash
+export PANMAN_BENCH_FULL=1   # bench.py prints the full report (as with --full): the lines below read it
 # Sweep-kernel variants and thresholds (bench lines only): tools/gpu_cl_sweep.sh TAG
 set -o pipefail
 cd "$(dirname "$0")/.."

@@ -1,4 +1,5 @@
 #!/bin/bash
+export PANMAN_BENCH_FULL=1   # bench.py prints the full report (as with --full): the lines below read it
 # The LDS-staged post-order sweeps on a GPU box: parity (tests/test_gpu_cluster.py), then
 # C3 / C4-T2 share / N* with the sweeps off and on (BENCH_ARGS appended), then a kernel trace
 # of C3 with the sweeps:  tools/gpu_cluster_ab.sh TAG

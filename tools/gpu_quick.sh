@@ -1,4 +1,5 @@
 #!/bin/bash
+export PANMAN_BENCH_FULL=1   # bench.py prints the full report (as with --full): the lines below read it
 # Fitch GPU tests (fast subset) + N* Fitch with (default build)
 set -o pipefail
 mkdir -p gpurun_out

@@ -1,4 +1,5 @@
 set -o pipefail
+export PANMAN_BENCH_FULL=1   # bench.py prints the full report (as with --full): the lines below read it
 mkdir -p gpurun_out
 (while true; do date >> gpurun_out/r06a_heartbeat.txt; sleep 30; done) &
 hb=$!

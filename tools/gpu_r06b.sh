@@ -1,4 +1,5 @@
 # cluster sweeps: GPU parity, then C3 / C4-T2 / N* with the sweeps off and on
+export PANMAN_BENCH_FULL=1   # bench.py prints the full report (as with --full): the lines below read it
 set -o pipefail
 mkdir -p gpurun_out
 timeout -k 10 600 python -u -m pytest tests/test_gpu_cluster.py -x -v --timeout 300 --timeout-method thread > gpurun_out/r06b_tests.log 2>&1

@@ -1,4 +1,5 @@
 #!/bin/bash
+export PANMAN_BENCH_FULL=1   # bench.py prints the full report (as with --full): the lines below read it
 # Cluster-count band rule (PM_CL_MAX_CLUSTERS) A/B on the C4 (T2) share and C3
 set -o pipefail
 cd "$(dirname "$0")/.."

@@ -1,4 +1,5 @@
 #!/bin/bash
+export PANMAN_BENCH_FULL=1   # bench.py prints the full report (as with --full): the lines below read it
 # GPU box: every -m gpu test, then the default bench line (driver-style).
 #   tools/gpu_round_check.sh TAG  ->  gpurun_out/gputests_TAG.log, gpurun_out/bench_default_TAG.json
 set -o pipefail

@@ -1,4 +1,5 @@
 #!/bin/bash
+export PANMAN_BENCH_FULL=1   # bench.py prints the full report (as with --full): the lines below read it
 # A/B of the pre-order level groups (PM_OPT_GROUP_WAVES / _LEVELS) on C3 / C2 / N* (GPU box,
 # repo root): VARIANTS="v1 v2" GRP="0 32768" LEVELS="2 3" NS=1 tools/group_ab.sh
 set -o pipefail

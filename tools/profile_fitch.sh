@@ -1,4 +1,5 @@
 #!/bin/bash
+export PANMAN_BENCH_FULL=1   # bench.py prints the full report (as with --full): the lines below read it
 # Profile the bench workload on a GPU box (run from the repo root):
 #   tools/profile_fitch.sh TAG [bench.py args]   ->  gpurun_out/prof_TAG/
 # Passes (separate runs, as the MI355X guide prescribes): kernel-trace stats, FETCH_SIZE,

@@ -1,4 +1,5 @@
 #!/bin/bash
+export PANMAN_BENCH_FULL=1   # bench.py prints the full report (as with --full): the lines below read it
 # PMC HBM traffic of the replay kernel (separate FETCH_SIZE / WRITE_SIZE passes):
 #   tools/profile_replay.sh TAG  ->  gpurun_out/prof_replay_TAG/{traffic.txt,traffic.json}
 set -euo pipefail

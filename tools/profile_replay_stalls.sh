@@ -1,4 +1,5 @@
 #!/bin/bash
+export PANMAN_BENCH_FULL=1   # bench.py prints the full report (as with --full): the lines below read it
 # Why the replay kernel writes at ~3 TB/s (review item 6): PMC passes over the C5 replay bench,
 # each its own run (counter limits per pass: 4 TCC, 8 SQ, 2 TA, 2 GRBM):
 #   tools/profile_replay_stalls.sh TAG  ->  gpurun_out/replay_stalls_TAG/{tcc,sq,ta}.txt

@@ -1,4 +1,5 @@
 #!/bin/bash
+export PANMAN_BENCH_FULL=1   # bench.py prints the full report (as with --full): the lines below read it
 # Replay-mode bench of library variants (tools/build_variant.sh), "base" = in-tree:
 #   tools/replay_variants.sh NAME...
 set -o pipefail

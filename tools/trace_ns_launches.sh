@@ -1,4 +1,5 @@
 #!/bin/bash
+export PANMAN_BENCH_FULL=1   # bench.py prints the full report (as with --full): the lines below read it
 # Per-launch kernel trace of one N* Fitch step (GPU box): gpurun_out/ns_launches_TAG.txt
 set -o pipefail
 cd "$(dirname "$0")/.."

@@ -1,4 +1,5 @@
 #!/bin/bash
+export PANMAN_BENCH_FULL=1   # bench.py prints the full report (as with --full): the lines below read it
 # rocprofv3 kernel-trace --stats of one bench command: tools/trace_stats.sh TAG [bench args]
 #   -> gpurun_out/trace_TAG/kernel_stats.csv (+ the bench line in gpurun_out/trace_TAG.json)
 set -euo pipefail

@@ -1,4 +1,5 @@
 #!/bin/bash
+export PANMAN_BENCH_FULL=1   # bench.py prints the full report (as with --full): the lines below read it
 # A/B of the grouped post-order launches (PM_OPT_UP_GROUP) and PM_UP_GROUP_NODES variants on
 # C3 / C2 / N* (GPU box, repo root): VARIANTS="v1 v2" tools/upgroup_ab.sh
 set -o pipefail

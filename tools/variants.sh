@@ -1,4 +1,5 @@
 #!/bin/bash
+export PANMAN_BENCH_FULL=1   # bench.py prints the full report (as with --full): the lines below read it
 # Bench experimental library variants (tools/build_variant.sh) side by side:
 #   tools/variants.sh NAME... [-- bench args]   ("base" = the in-tree library)
 set -o pipefail
