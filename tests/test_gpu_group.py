@@ -42,6 +42,7 @@ def test_groups_equal_levels(engine, variant, narrow, levels, tree):
     else:
         off, idx, root = panman_amd.random_join_tree(6000, seed=22)
     _variant(engine, variant)
+    engine.set_cluster(panman_amd.engine.CLUSTER_DEFAULT)   # (whatever an earlier test left)
     engine.tree_upload(off, idx, root)
     engine.synth_columns(0, 4500, seed=5)
     try:
@@ -102,6 +103,7 @@ def test_up_groups_equal_heights(engine, narrow, tree, mode):
     else:
         off, idx, root = random_tree(3000, np.random.default_rng(34), max_children=300, unary=0.0)
     _variant(engine, "virtual")
+    engine.set_cluster(panman_amd.engine.CLUSTER_DEFAULT)   # (whatever an earlier test left)
     engine.tree_upload(off, idx, root)
     engine.synth_columns(0, 4500, seed=6)
     res = []
@@ -132,6 +134,7 @@ def test_plain_up_equals_general_kernel(engine, narrow, tree, mode):
     else:
         off, idx, root = random_tree(3000, np.random.default_rng(43), max_children=3, unary=0.05)
     _variant(engine, "virtual")
+    engine.set_cluster(panman_amd.engine.CLUSTER_DEFAULT)   # (whatever an earlier test left)
     engine.tree_upload(off, idx, root)
     engine.synth_columns(0, 4500, seed=7)
     res = []
@@ -157,6 +160,7 @@ def test_sankoff_groups_equal_levels(engine, mode, levels, narrow):
     rng = np.random.default_rng(90 + levels)
     off, idx, root = panman_amd.sars_like_tree(4000, seed=41) if mode == panman_amd.MODE_SANKOFF else \
         random_tree(600, rng, max_children=5, unary=0.1)
+    engine.set_cluster(panman_amd.engine.CLUSTER_DEFAULT)   # (whatever an earlier test left)
     engine.tree_upload(off, idx, root)
     if mode == panman_amd.MODE_SANKOFF:
         engine.synth_columns(0, 3000, seed=7)

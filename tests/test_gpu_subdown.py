@@ -33,6 +33,7 @@ def test_sub_down_equals_tail(engine, tree, narrow, group):
         off, idx, root = panman_amd.sars_like_tree(6000, seed=31)
     else:
         off, idx, root = panman_amd.random_join_tree(8000, seed=32)
+    engine.set_cluster(panman_amd.engine.CLUSTER_DEFAULT)   # (whatever an earlier test left)
     engine.tree_upload(off, idx, root)
     engine.synth_columns(0, 4500, seed=7)
     engine.set_narrow(narrow)
@@ -53,6 +54,7 @@ def test_sub_down_equals_tail(engine, tree, narrow, group):
 def test_sub_down_vs_oracle(engine, oracle, seed):
     leaves, sites = [2000, 3001, 777][seed], [777, 2049, 4099][seed]
     off, idx, root = panman_amd.random_join_tree(leaves, seed=40 + seed)
+    engine.set_cluster(panman_amd.engine.CLUSTER_DEFAULT)
     engine.tree_upload(off, idx, root)
     engine.synth_columns(0, sites, seed=9 + seed)
     got = _run(engine, True)[0]
