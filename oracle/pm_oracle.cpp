@@ -1471,6 +1471,16 @@ std::string reroot_dump(RTree& t, const std::string& name) {
 char* oracle_fasta(const OraclePanmat* p, int aligned, int leaf_limit, int threads, double* seconds) {
     RTree t;
     build_rtree(p, t);
+    // blockSequence, sequence, blockExists and blockStrand have blocks.size() + 1 entries indexed
+    // by block id (src/fasta.cpp:2001-2012): an id beyond that is outside what
+    // printFASTAUltraFast can replay
+    const int32_t id_end = (int32_t)t.blocks.size() + 1;
+    bool ids_ok = true;
+    for (auto& b : t.blocks) ids_ok &= b.primary >= 0 && b.primary < id_end;
+    for (auto& g : t.gaps) ids_ok &= g.primary >= 0 && g.primary < id_end;
+    for (auto& kv : t.all)
+        for (auto& m : kv.second->bmuts) ids_ok &= m.primary >= 0 && m.primary < id_end;
+    if (!ids_ok) return dup_string("#error\tblock id beyond the block count\n");
     std::vector<RNode*> leaves;
     for (auto& kv : t.all) {
         if (!kv.second->children.empty()) continue;

@@ -221,7 +221,10 @@ hipError_t d2h_stream(pm_ctx* c, const void* src, size_t n, const std::function<
                       bool& sink_ok) {
     sink_ok = true;
     if (n == 0) return hipSuccess;
-    hipError_t e = hipSuccess;
+    // (pm_fasta_multi_fd streams every shard from one host thread: the stage buffer and the
+    // events belong on the shard's device, not on whichever the thread used last)
+    hipError_t e = hipSetDevice(c->device);
+    if (e != hipSuccess) return e;
     if (!c->stage) {
         if ((e = hipHostMalloc(&c->stage, kStageChunk * kStageSlots, hipHostMallocDefault)) != hipSuccess) {
             c->stage = nullptr;

@@ -9,6 +9,7 @@ import pytest
 
 import panman_amd
 from _panmat import random_panmat, tree_dump
+from _replay_shapes import caterpillar
 from _trees import names_for, parse_newick, to_newick
 from panman_amd._lib import phase_report, phase_reset
 from panman_amd.engine import sars_like_tree
@@ -26,24 +27,6 @@ def engine():
 
 def _records(text):
     return sorted(">" + r for r in text.split(">")[1:])
-
-
-def caterpillar(leaves: int):
-    """((((s0,s1),s2),s3)...): leaf k hangs off spine node k; depth = leaves - 1."""
-    n = 2 * leaves - 1
-    kids = {}
-    cur = 0
-    nxt = leaves
-    for k in range(1, leaves):
-        kids[nxt] = [cur, k]
-        cur = nxt
-        nxt += 1
-    off = np.zeros(n + 1, np.int32)
-    idx = []
-    for v in range(n):
-        idx += kids.get(v, [])
-        off[v + 1] = len(idx)
-    return off, np.array(idx, np.int32), cur
 
 
 def _fasta_checked(engine, pm, aligned, min_chunks=2):
