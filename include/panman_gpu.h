@@ -110,6 +110,14 @@ int pm_set_stream(pm_ctx* ctx, void* hip_stream);
  *   PM_OPT_SUB_DOWN (default 0): Fitch, subtree form -- a three- or four-leaf subtree's
  *                  finals and records come from its parent's pre-order wave instead of a
  *                  wave of their own after the levels.
+ *   PM_OPT_TAIL_PACK (default 1): Fitch, subtree form -- the tail launch's three- and
+ *                  four-leaf subtrees run eight consecutive items per wave, the dirty (item,
+ *                  word) pairs of the eight gathered into full waves, instead of one wave per
+ *                  (item, tile) with only its dirty lanes busy; the other tail items keep
+ *                  their own launch -- when those subtrees make at least 65536 (item, tile)
+ *                  waves: a launch the chip holds at once is no faster packed.  A value >= 2
+ *                  sets that threshold, -1 packs at any size, 0 = one wave per item.  Results
+ *                  identical.  Sankoff and PM_OPT_SUB_DOWN runs do not use it.
  *   PM_OPT_PLAIN_UP (default 1): Fitch / Sankoff, grouped subtree form -- a post-order launch's binary
  *                  nodes with no three- / four-leaf subtree child and nothing recomputed run in
  *                  a lean kernel (fewer registers, more waves in flight) before the rest, when
@@ -148,6 +156,7 @@ int pm_set_stream(pm_ctx* ctx, void* hip_stream);
 #define PM_OPT_PLAIN_UP 14
 #define PM_OPT_NT_LOADS 16
 #define PM_OPT_CLUSTER 17
+#define PM_OPT_TAIL_PACK 18
 int pm_set_option(pm_ctx* ctx, int option, int64_t value);
 /* Accumulate per-kernel-class device time with HIP events (see pm_kernel_times). */
 int pm_set_profiling(pm_ctx* ctx, int enable);

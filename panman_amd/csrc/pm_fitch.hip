@@ -992,13 +992,32 @@ hipError_t launch_fitch(pm_ctx* c, bool block) {
     // The tail (children beyond the second, S2 / S3 subtrees) needs only its parents'
     // finals: one flat launch after the levels.
     // (PM_OPT_SUB_DOWN: the S2 / S3 items, the first num_tail_s, were done by the levels)
-    const int32_t tail_skip = sub_down ? ht.num_tail_s : 0;
+    // (PM_OPT_TAIL_PACK: the S2 / S3 items in groups per wave, k_tail<.., G>; the other items
+    // -- leaf-ish children beyond the second -- after them, one wave each as before)
+    const int64_t pack_min = c->tail_pack_min_waves != 0 ? c->tail_pack_min_waves : kTailPackMinWaves;
+    const bool pack = sub && !sub_down && c->tail_pack && ht.num_tail_s > 0 && (int64_t)ht.num_tail_s * tiles >= pack_min;
+    constexpr int G = kTailPack;
+    phase_add("run.tail_pack", pack ? (double)G : 0.0);   // the group size a launch sequence took (0: one wave per item)
+    phase_add("run.tail_s_waves", sub ? (double)ht.num_tail_s * tiles : 0.0);   // ... and what the threshold is compared with
+    if (pack) {
+        DownArgs t = dn;
+        t.tail = dt.tail_desc_k;
+        t.num_s = ht.num_tail_s;
+        t.count = (ht.num_tail_s + G - 1) / G;
+        t.sbase = ht.sbase;
+        t.sub_planes = c->sub_planes;
+        const dim3 grid = wave_grid(t.count, tiles);
+        timer_begin(c, 5);
+        hipLaunchKernelGGL((k_tail<Mode::kFitch, true, true, G>), grid, dim3(kBlock), 0, c->stream, t);
+        timer_end(c, 5);
+    }
+    const int32_t tail_skip = sub_down || pack ? ht.num_tail_s : 0;
     const int32_t tail_total = (sub ? ht.num_tail_k : virt ? ht.num_tail_v : ht.num_tail) - tail_skip;
     if (tail_total > 0) {
         DownArgs t = dn;
         t.tail = (sub ? dt.tail_desc_k : virt ? dt.tail_desc_v : dt.tail_desc) + tail_skip;
         t.count = tail_total;
-        t.num_s = sub && !sub_down ? ht.num_tail_s : 0;
+        t.num_s = sub && !sub_down && !pack ? ht.num_tail_s : 0;
         t.sbase = ht.sbase;
         t.sub_planes = c->sub_planes;
         const dim3 grid = wave_grid(t.count, tiles);

@@ -308,6 +308,8 @@ struct pm_ctx {
     int32_t group_levels = 4;         // ... and up to this many levels (PM_OPT_GROUP_LEVELS)
     bool up_group = true;             // Fitch subtree form: grouped post-order launches (PM_OPT_UP_GROUP)
     bool sub_down = false;            // Fitch subtree form: S2 / S3 records in their parent's pre-order wave (PM_OPT_SUB_DOWN)
+    bool tail_pack = true;            // Fitch subtree form: the tail's S2 / S3 items in groups per wave, dirty words gathered into full waves (PM_OPT_TAIL_PACK)
+    int64_t tail_pack_min_waves = 0;  // ... from this many (S item, tile) waves (0: kTailPackMinWaves, -1: always)
     bool plain_up = true;             // grouped subtree form: plain nodes in the lean post-order kernels (PM_OPT_PLAIN_UP)
     int64_t plain_min_waves = 0;      // ... from this many (node, tile) waves (0: kPlainMinWaves)
     bool cluster = true;              // Fitch subtree form: LDS-staged post-order sweeps above ht.cl.h0 (PM_OPT_CLUSTER)

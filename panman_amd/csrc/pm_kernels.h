@@ -1158,8 +1158,9 @@ __device__ __forceinline__ void emit_flush(const Args& a, Emit& em, int lane) {
     em.cnt = 0;
 }
 
-// Stage one stream: node id (wave-uniform), diff mask D, the child's code planes c, the
-// parent's code planes pc.  Every lane of the wave calls it.
+// Stage one stream: node id and site0 (per lane: each entry stores its own; wave-uniform in
+// every kernel but the packed tail), diff mask D, the child's code planes c, the parent's
+// code planes pc.  Every lane of the wave calls it.
 template <class Args>
 __device__ __forceinline__ void emit_stream(const Args& a, Emit& em, int lane, uint32_t node, uint32_t D, uint32_t site0,
                                             uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, const uint32_t* pc) {
@@ -1398,7 +1399,9 @@ __device__ __forceinline__ void emit_code(const Args& a, Emit& em, int lane, uin
 
 // Records of an S2 / S3 subtree: v, x, a, b, c (S2: c under v) [, y, d]; ids = the
 // child's node id, then its leaves' (id[1..4]), cherries ix / iy.
-template <Mode M, class Args>
+// LANES: ids, shape, site0 differ from lane to lane (packed tail): every lane stages all seven
+// streams, an S2 lane's last two with an empty mask (emit_stream's ballots need the whole wave).
+template <Mode M, bool LANES = false, class Args>
 __device__ __forceinline__ void subtree_emit(const Args& a, Emit& em, int lane, const int32_t* id, int32_t ix, int32_t iy,
                                              const Kid& k, int sh, uint32_t valid, const uint32_t* Fn, uint32_t site0) {
     const uint4 P = make_uint4(Fn[0], Fn[1], Fn[2], Fn[3]);
@@ -1410,9 +1413,10 @@ __device__ __forceinline__ void subtree_emit(const Args& a, Emit& em, int lane, 
     emit_code(a, em, lane, (uint32_t)id[2], msk & code_ne(k.L1, f.G), site0, k.L1, f.G);
     const uint4 pc = sh == 1 ? f.F : f.H;
     emit_code(a, em, lane, (uint32_t)id[3], msk & code_ne(k.L2, pc), site0, k.L2, pc);
-    if (sh == 2) {
-        emit_code(a, em, lane, (uint32_t)iy, msk & code_ne(f.H, f.F), site0, f.H, f.F);
-        emit_code(a, em, lane, (uint32_t)id[4], msk & code_ne(k.L3, f.H), site0, k.L3, f.H);
+    if (LANES || sh == 2) {
+        const uint32_t m3 = sh == 2 ? msk : 0u;
+        emit_code(a, em, lane, (uint32_t)iy, m3 & code_ne(f.H, f.F), site0, f.H, f.F);
+        emit_code(a, em, lane, (uint32_t)id[4], m3 & code_ne(k.L3, f.H), site0, k.L3, f.H);
     }
 }
 
@@ -1755,14 +1759,136 @@ __global__ __launch_bounds__(kBandBlock) void k_down_band(DownArgs a, const int3
 #ifndef PM_TAIL_WAVES
 #define PM_TAIL_WAVES 6
 #endif
-template <Mode M, bool AP, bool SUB = false>
-__global__ __launch_bounds__(kBlock, SUB ? PM_TAIL_WAVES : 1) void k_tail(DownArgs a) {
+// Packed tail (PM_OPT_TAIL_PACK): one wave = G consecutive S2 / S3 items at one tile, their
+// dirty (item, word) pairs gathered into full waves.  An item's wave of its own keeps about
+// one lane in five busy (the parent's dirty lanes, RecMask::d); here slot j of the group's T
+// dirty pairs goes to lane j % 64 of round j / 64, so a round's loads are 64 lanes' lines in
+// flight and its finals and record streams are computed by 64 busy lanes.
+//   lane g < G loads item g's pushed masks (push_sub) and descriptor and leaves them in LDS;
+//   each dirty lane l of item g writes g * 64 + l at slot prefix[g] + lanes_below(md_g);
+//   lane j then reads its slot, and through it its item's descriptor and parent masks.
+// Bytes and lines read are those of the items' own waves (same addresses, dirty lanes only).
+// G = 4, 8 and 16 measured alike at N* (k_tail 1.36 ms each, 2.17 ms unpacked); 8 keeps seven
+// waves per SIMD (68 VGPRs, 22 KiB of LDS per block), 16 would drop to five (28 KiB).
+#ifndef PM_TAIL_PACK
+#define PM_TAIL_PACK 8
+#endif
+#ifndef PM_TAIL_PACK_WAVES
+#define PM_TAIL_PACK_WAVES 6
+#endif
+constexpr int kTailPack = PM_TAIL_PACK;
+// ... from this many (S item, tile) waves of the unpacked launch: eight times the 8192 waves the
+// chip holds.  A launch that fits the chip at once has every item's loads in flight together
+// already, and a group's rounds only run one behind the other (C2, a few thousand such waves:
+// 0.1838 -> 0.1857 ms per step packed; N*, about 3M: 14.16 -> 13.24 ms).
+#ifndef PM_TAIL_PACK_MIN_WAVES
+#define PM_TAIL_PACK_MIN_WAVES 65536
+#endif
+constexpr int64_t kTailPackMinWaves = PM_TAIL_PACK_MIN_WAVES;
+constexpr int kPackInfoQuads = 4;   // per item: {parent, enc, ix, iy}, id[0..3], {id[4], 0, 0, 0}, {px, ps}
+
+__device__ __forceinline__ uint32_t bits_below(uint64_t m, uint32_t l) {   // set bits of m below bit l (l per lane)
+    return (uint32_t)__builtin_popcountll(m & ((1ull << l) - 1ull));
+}
+
+template <Mode M, int G>
+__device__ __forceinline__ void tail_packed(const DownArgs& a, int32_t group, int tile, int lane, uint4* stage, uint4* info,
+                                            uint16_t* slots) {
+    constexpr int REC = M == Mode::kSankoff ? kSankoffRec : kFitchRec;
+    const int32_t item0 = group * G;
+    // lane g: item g's masks (parent x, parent s, dirty lanes) and descriptor, in flight together
+    const int32_t mine = item0 + lane;
+    const bool own = lane < G && mine < a.num_s;
+    uint64_t px = 0, ps = 0, md = 0;
+    uint4 d0 = make_uint4(0, 0, 0, 0), d2 = make_uint4(0, 0, 0, 0);
+    uint32_t id4 = 0;
+    if (own) {
+        const uint64_t* q = a.cmask + kMaskWords * ((size_t)(a.sbase + mine) * a.tiles + tile);
+        px = q[3];
+        ps = q[4];
+        md = q[5];
+        const uint4* tp = reinterpret_cast<const uint4*>(a.tail + mine);
+        d0 = tp[0];
+        d2 = tp[2];
+        id4 = (uint32_t)a.tail[mine].id[4];
+    }
+    if (own && (int32_t)d0.x == a.root_dense) md = ~0ull;   // every lane dirty under the root
+    uint32_t T;
+    const uint32_t pre = wave_exclusive_scan((uint32_t)__builtin_popcountll(md), T);
+    if (T == 0) return;   // no dirty lane in the group: the children hold their parents' codes
+    if (lane < G) {
+        uint4* w = info + lane * kPackInfoQuads;
+        w[0] = d0;
+        w[1] = d2;
+        w[2] = make_uint4(id4, 0u, 0u, 0u);
+        w[3] = make_uint4((uint32_t)px, (uint32_t)(px >> 32), (uint32_t)ps, (uint32_t)(ps >> 32));
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)md, g), hi = __builtin_amdgcn_readlane((uint32_t)(md >> 32), g);
+        const uint64_t m = (uint64_t)lo | ((uint64_t)hi << 32);   // (readlane returns int: widened unsigned)
+        const uint32_t p = __builtin_amdgcn_readlane(pre, g);
+        if ((m >> lane) & 1ull) slots[p + lanes_below(m)] = (uint16_t)(g * kWave + lane);
+    }
+    __builtin_amdgcn_wave_barrier();   // (one wave: its LDS writes land before its later reads)
+    // (salted by the group, not its first item: a multiple of G reaches only kShards / G shards per tile)
+    Emit em{stage, shard_of((uint32_t)group, tile), 0u, 0u};
+    for (uint32_t r0 = 0; r0 < T; r0 += kWave) {
+        const uint32_t j = r0 + (uint32_t)lane;
+        const bool act = j < T;   // (an idle lane of the last round: the round's first slot, nothing loaded or emitted)
+        const uint32_t slot = slots[act ? j : r0];
+        const uint32_t g = slot >> 6, l = slot & 63u;
+        const uint4* w = info + g * kPackInfoQuads;
+        const uint4 i0 = w[0], i1 = w[1], i2 = w[2], i3 = w[3];
+        const int32_t parent = (int32_t)i0.x, enc = (int32_t)i0.y;
+        const int sh = kid_shape(enc);
+        const int64_t word = (int64_t)tile * kWave + l;
+        const uint32_t valid = act ? valid_mask(a, word) : 0u;
+        // every load of the round issued before any is consumed ("initialise, then exec-masked
+        // load", see kid_fetch): the leaves' words side by side, the parent's final
+        Kid k;
+        k.enc = enc;
+        k.L0 = k.L1 = k.L2 = k.L3 = make_uint4(0, 0, 0, 0);
+        k.m0 = k.m1 = 0;
+        const uint4* q = sub_word(a.sub_planes, item0 + (int32_t)g, a.wpad, word);
+        if (act) {
+            k.L0 = q[0];
+            k.L1 = q[1];
+            k.L2 = q[2];
+            k.m0 = k.m1 = ~0u;
+        }
+        if (act && sh == 2) k.L3 = q[3];
+        const uint64_t mx = (uint64_t)i3.x | ((uint64_t)i3.y << 32), ms = (uint64_t)i3.z | ((uint64_t)i3.w << 32);
+        const uint4* pb = a.sets + ((size_t)parent * a.tiles + tile) * REC;
+        const uint4* fsrc = parent == a.root_dense ? a.root_final + word
+                            : ((mx >> l) & 1ull)   ? pb + (uint32_t)__builtin_popcountll(ms) + bits_below(mx, l)
+                            : ((ms >> l) & 1ull)   ? pb + bits_below(ms, l)
+                                                   : a.cons + word;
+        uint4 pf = make_uint4(0, 0, 0, 0);
+        if (act) pf = *fsrc;
+        const uint32_t F[4] = {pf.x, pf.y, pf.z, pf.w};
+        const int32_t id[5] = {(int32_t)i1.x, (int32_t)i1.y, (int32_t)i1.z, (int32_t)i1.w, (int32_t)i2.x};
+        subtree_emit<M, true>(a, em, lane, id, (int32_t)i0.z, (int32_t)i0.w, k, sh, valid, F, (uint32_t)(word * 32));
+    }
+    emit_flush<M != Mode::kSankoff>(a, em, lane);
+}
+
+// G > 0: the packed form -- items [0, num_s) in groups of G, a.count groups.
+template <Mode M, bool AP, bool SUB = false, int G = 0>
+__global__ __launch_bounds__(kBlock, G > 0 ? PM_TAIL_PACK_WAVES : SUB ? PM_TAIL_WAVES : 1) void k_tail(DownArgs a) {
     __shared__ uint4 stage[kWavesPerBlock][kEntryQuads];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     int32_t item;
     int tile;
     wave_item(wave, a.tiles, item, tile);
     if (item >= a.count) return;
+    if constexpr (G > 0) {
+        static_assert(SUB && AP && G <= kWave && G * kWave <= 65536, "packed tail: S2 / S3 items, slot = g * 64 + lane in 16 bits");
+        __shared__ uint4 info[kWavesPerBlock][G * kPackInfoQuads];
+        __shared__ uint16_t slots[kWavesPerBlock][G * kWave];
+        tail_packed<M, G>(a, item, tile, lane, stage[wave], info[wave], slots[wave]);
+        return;
+    }
     const TailDesc& t = a.tail[item];
     const int64_t word = (int64_t)tile * kWave + lane;
     const uint32_t valid = valid_mask(a, word);
