@@ -141,6 +141,10 @@ int pm_set_stream(pm_ctx* ctx, void* hip_stream);
  *                  0 = the level kernels everywhere.  A value >= 2 instead takes every height
  *                  from the first whose level (and every level above it) holds at most that
  *                  many nodes.  Takes effect at the next pm_tree_upload; results identical.
+ *   PM_OPT_VCF_BATCH_BYTES (default 1 GiB, at least 4096): pm_vcf / pm_vcf_fd produce and
+ *                  stream the genotype text in batches of whole lines of at most this many
+ *                  bytes (always at least one line), so the device never holds lines x samples
+ *                  at once.  The text does not depend on it.
  * (Option ids 1, 4, 5 and 11 -- subtree-region, heavy-path-chain and level-band schedules,
  * tail records overlapped with the pre-order levels -- were measured slower than, or no
  * faster than, the level kernels on MI355X and removed.) */
@@ -157,6 +161,7 @@ int pm_set_stream(pm_ctx* ctx, void* hip_stream);
 #define PM_OPT_NT_LOADS 16
 #define PM_OPT_CLUSTER 17
 #define PM_OPT_TAIL_PACK 18
+#define PM_OPT_VCF_BATCH_BYTES 19
 int pm_set_option(pm_ctx* ctx, int option, int64_t value);
 /* Accumulate per-kernel-class device time with HIP events (see pm_kernel_times). */
 int pm_set_profiling(pm_ctx* ctx, int enable);
@@ -386,6 +391,29 @@ int pm_replay_format_fd(pm_ctx* ctx, int aligned, int fd, int64_t* length);
 int pm_fasta_fd(pm_ctx* ctx, const pm_panmat* panmat, int aligned, int fd, int64_t* length);
 int pm_fasta_multi_fd(const pm_panmat* panmat, int aligned, const int* devices, int num_devices, int fd, int64_t* length,
                       char* err, int64_t err_len);
+/* Drop-in for Tree::printVCFParallel(refnode, fout) (src/vcf.cpp:177-382; the --vcf command,
+ * src/panmanUtils.cpp:654-697): the variants of every tip against the tip named `reference`.
+ * A tip's row is what pm_fasta(aligned = 1) prints for it without the line breaks (block print
+ * order, rotation, inversion, strands and absent-block dashes included); a tip whose row
+ * length differs from the reference tip's is not compared (vcf.cpp:229-232): it stays a sample
+ * column of zeros and is counted in `*skipped` (nullable).  Each compared tip is scanned left
+ * to right with the reference's rules (differences merge until the next column where both
+ * rows hold the same base, which anchors the next difference; a leading insertion is closed by
+ * that base instead).  Text: the four ## header lines (fileDate = year, month, day unpadded,
+ * local time), the #CHROM line with the samples -- every tip but the reference in byte order
+ * of the names -- and one line per distinct (POS, REF) in (POS, REF bytes) order, ID the
+ * running line number from 0, ALT the distinct ALTs in byte order (an empty REF or ALT is "."),
+ * ".\t.\t.\t.", then per sample the 1-based index of its ALT, or 0.
+ * The rows are replayed and compared on the GPU (profiling class 3); the host groups the
+ * records into lines; the genotype text is produced on the device in batches
+ * (PM_OPT_VCF_BATCH_BYTES) and streamed through the pinned download slots.  Phase log: vcf.*.
+ * `*text` is malloc'd (release with pm_free); pm_vcf_fd writes to `fd` instead (`length`
+ * nullable).  Errors: an unknown `reference`, one that is not a tip, or fewer than two tips:
+ * PM_ERR_ARG; a failed write: PM_ERR_ARG (errno kept), as pm_fasta_fd. */
+int pm_vcf(pm_ctx* ctx, const pm_panmat* panmat, const char* reference, char** text, int64_t* length,
+           int64_t* skipped);
+int pm_vcf_fd(pm_ctx* ctx, const pm_panmat* panmat, const char* reference, int fd, int64_t* length,
+              int64_t* skipped);
 /* Canonical aligned columns per leaf of the prepared PanMAT (gap slots before each main
  * position, block sentinels included) and the number of leaves. */
 int pm_replay_shape(pm_ctx* ctx, int64_t* leaves, int64_t* columns, int64_t* edits);

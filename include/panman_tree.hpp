@@ -123,6 +123,18 @@ class Tree {
         pm_free(text);
     }
 
+    // Tree::printVCFParallel(refnode, fout) (src/vcf.cpp:177-382), the reference tip given by
+    // name; a name that is no tip throws where the reference prints "Reference not set correctly".
+    void printVCFParallel(const std::string& reference, std::ostream& fout) const {
+        detail::Ctx ctx(device_);
+        pm_panmat v = view();
+        char* text = nullptr;
+        int64_t len = 0;
+        ctx.check(pm_vcf(ctx.c, &v, reference.c_str(), &text, &len, nullptr), "pm_vcf");
+        fout.write(text, (std::streamsize)len);
+        pm_free(text);
+    }
+
     // Tree::printSummary(out) (src/summary.cpp:257-273); the block lines go to std::cout as
     // getBlockMutationsParallel prints them (:203-250).
     void printSummary(std::ostream& out) const {

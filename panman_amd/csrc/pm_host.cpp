@@ -448,7 +448,7 @@ int pm_warmup(int device) {
     if (e != hipSuccess || n == 0) return PM_ERR_HIP;
     if (device < 0 || device >= n) return PM_ERR_ARG;
     if ((e = hipSetDevice(device)) != hipSuccess) return PM_ERR_HIP;
-    for (auto warm : {warm_fitch, warm_sankoff, warm_fitch_nt, warm_sankoff_nt, warm_replay, warm_synth, warm_sort})
+    for (auto warm : {warm_fitch, warm_sankoff, warm_fitch_nt, warm_sankoff_nt, warm_replay, warm_synth, warm_sort, warm_vcf})
         if ((e = warm()) != hipSuccess) return PM_ERR_HIP;
     // the runtime's first allocation and staged copies
     void* d = nullptr;
@@ -525,6 +525,11 @@ int pm_set_option(pm_ctx* c, int option, int64_t value) {
         if (value < -1) return fail(c, PM_ERR_ARG, "PM_OPT_TAIL_PACK: -1, 0, 1 or a wave threshold >= 2");
         c->tail_pack = value != 0;
         c->tail_pack_min_waves = value >= 2 ? value : value < 0 ? -1 : 0;
+        return PM_OK;
+    }
+    if (option == PM_OPT_VCF_BATCH_BYTES) {
+        if (value < 4096) return fail(c, PM_ERR_ARG, "PM_OPT_VCF_BATCH_BYTES: at least 4096");
+        c->vcf_batch_bytes = value;
         return PM_OK;
     }
     if (option == PM_OPT_GROUP_WAVES) {

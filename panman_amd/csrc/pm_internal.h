@@ -385,6 +385,8 @@ struct pm_ctx {
     size_t text_cap = 0;
     void* rows_buf = nullptr;
     size_t rows_cap = 0;
+
+    int64_t vcf_batch_bytes = (int64_t)1 << 30;   // pm_vcf: genotype text per device batch (PM_OPT_VCF_BATCH_BYTES)
 };
 
 namespace pm {
@@ -553,6 +555,56 @@ struct FmtArgs {
 hipError_t launch_fmt_count(pm_ctx* c, const FmtArgs& f, int32_t leaves);
 hipError_t launch_fmt_write(pm_ctx* c, const FmtArgs& f, int32_t leaves);
 hipError_t launch_replay(pm_ctx* c, const ReplayDev& d);
+
+// VCF extraction (pm_vcf.hip; printVCFParallel, src/vcf.cpp:177-382) over the aligned FASTA text
+// of format_device: column i of a leaf's row is text[row_base[leaf] + i + i / 70].
+struct VcfRec {
+    int32_t leaf, pos;     // the tip (replay leaf index) and POS
+    int64_t off;           // REF at pool[off .. off + rlen), ALT behind it
+    int32_t rlen, alen;
+};
+struct VcfArgs {
+    const char* text;
+    const int64_t* row_base;   // [leaves]
+    const uint8_t* live;       // [leaves] 1: compared (not the reference, same row length)
+    int32_t leaves;
+    int32_t ref_leaf;
+    int64_t n;                 // columns of the reference row
+    int64_t words;             // 64-column words per leaf
+    char* ref;                 // [n] the reference row without line breaks
+    int32_t* coord;            // [n] POS of a column: 1 + reference bases before it
+    uint64_t* skip;            // [leaves][words] both rows '-' (and the columns past n)
+    uint64_t* equal;           // [leaves][words] the same base in both rows
+    int64_t* nstart;           // [leaves + 1] events per leaf, then their exclusive scan
+    int64_t* chain;            // [leaves] first column whose equal base anchors (n: none)
+    int64_t events;
+    int32_t* ev_leaf;          // [events]
+    int32_t* ev_col;           // [events] first column of the event
+    int64_t* ev_recs;          // [events + 1] 1: the event yields a record; then the scan
+    int64_t* ev_bytes;         // [events + 1] its REF + ALT bytes; then the scan
+    VcfRec* recs;
+    char* pool;
+};
+hipError_t launch_vcf_classify(pm_ctx* c, const VcfArgs& a);            // ref, coord, planes, nstart, chain
+hipError_t launch_vcf_list(pm_ctx* c, const VcfArgs& a);                // ev_leaf / ev_col from the scanned nstart
+hipError_t launch_vcf_emit(pm_ctx* c, const VcfArgs& a, bool write);    // count, or records + pool
+// exclusive scan in place of v[0 .. n] (v[n] receives the total)
+hipError_t vcf_scan(pm_ctx* c, int64_t* v, int64_t n);
+// Genotype text of a batch of lines: cells (line in batch, sample, ALT index), per line the
+// host's prefix; line lengths, offsets and text on the device.
+struct VcfTextArgs {
+    int32_t lines, samples;
+    int64_t cells;
+    const int32_t* cell;        // [cells][3]
+    uint32_t* gt;               // [lines][samples]
+    const int64_t* prefix_off;  // [lines + 1] into prefix
+    const char* prefix;
+    int64_t* line_off;          // [lines + 1] lengths, then their exclusive scan
+    char* text;
+};
+hipError_t launch_vcf_text_count(pm_ctx* c, const VcfTextArgs& t);
+hipError_t launch_vcf_text_write(pm_ctx* c, const VcfTextArgs& t);
+hipError_t warm_vcf();
 // rows[leaf][c0 .. c0+n) chars -> packed codes out[leaf][(n+1)/2] ('-', 'x' -> 0)
 hipError_t launch_rows_to_codes(pm_ctx* c, const char* rows, int64_t row_stride, int32_t leaves, int64_t c0,
                                 int64_t n, uint8_t* out, int64_t out_stride);

@@ -634,8 +634,10 @@ void free_replay(pm_ctx* c) {
 
 namespace pm {
 // The FASTA text of the replayed rows in the context's device text buffer (c->text_buf),
-// `total` bytes; `clock` carries on into the caller's download phase.
-int format_device(pm_ctx* c, int aligned, int64_t& total, PhaseClock& clock) {
+// `total` bytes; `clock` carries on into the caller's download phase.  row_base / row_len
+// (nullable): per leaf the text offset of its first sequence character and its line length.
+int format_device(pm_ctx* c, int aligned, int64_t& total, PhaseClock& clock, std::vector<int64_t>* row_base,
+                  std::vector<int64_t>* row_len) {
     if (!c) return PM_ERR_ARG;
     if (!c->replay || !c->replay->ran) return fail(c, PM_ERR_STATE, "run the replay first");
     (void)hipSetDevice(c->device);
@@ -722,6 +724,11 @@ int format_device(pm_ctx* c, int aligned, int64_t& total, PhaseClock& clock) {
         text_off[li + 1] = text_off[li] + hdr + p + p / 70 + 1;
     }
     total = text_off[L];
+    if (row_base) {
+        row_base->resize(L);
+        for (int32_t li = 0; li < L; ++li) (*row_base)[li] = text_off[li] + (name_off[li + 1] - name_off[li] + 2);
+    }
+    if (row_len) *row_len = line;
     clock.lap("fasta.count");
     if ((e = dput(&d_off, off, c->stream)) != hipSuccess || (e = dput(&d_line, line, c->stream)) != hipSuccess ||
         (e = dput(&d_start, start, c->stream)) != hipSuccess || (e = dput(&d_text_off, text_off, c->stream)) != hipSuccess ||
@@ -826,7 +833,9 @@ int pm_replay_format_fd(pm_ctx* c, int aligned, int fd, int64_t* length) {
     return PM_OK;
 }
 
-namespace {
+}  // extern "C"
+
+namespace pm {
 // prepare + replay (+ the depth-first kernel's rebuild count in the phase log)
 int fasta_replay(pm_ctx* c, const pm_panmat* p) {
     int rc = pm_replay_prepare(c, p);
@@ -844,7 +853,9 @@ int fasta_replay(pm_ctx* c, const pm_panmat* p) {
     }
     return rc;
 }
-}  // namespace
+}  // namespace pm
+
+extern "C" {
 
 int pm_fasta_fd(pm_ctx* c, const pm_panmat* p, int aligned, int fd, int64_t* length) {
     int rc = fasta_replay(c, p);

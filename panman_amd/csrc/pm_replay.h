@@ -79,4 +79,11 @@ struct ReplayHost {
 int replay_flatten(const pm_panmat* p, ReplayState& r, ReplayHost& h, int64_t leaf_begin, int64_t leaf_end,
                    std::string& err_msg);
 
+// prepare + replay of every leaf (pm_fasta's first half); the rows stay in c->replay.
+int fasta_replay(pm_ctx* c, const pm_panmat* p);
+// The FASTA text of the replayed rows in c->text_buf (`total` bytes).  row_base / row_len
+// (nullable): per leaf the text offset of its first sequence character and its line length.
+int format_device(pm_ctx* c, int aligned, int64_t& total, PhaseClock& clock, std::vector<int64_t>* row_base = nullptr,
+                  std::vector<int64_t>* row_len = nullptr);
+
 }  // namespace pm
