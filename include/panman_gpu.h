@@ -145,6 +145,9 @@ int pm_set_stream(pm_ctx* ctx, void* hip_stream);
  *                  stream the genotype text in batches of whole lines of at most this many
  *                  bytes (always at least one line), so the device never holds lines x samples
  *                  at once.  The text does not depend on it.
+ *   PM_OPT_MAF_BATCH_BYTES (default 1 GiB, at least 4096): pm_maf / pm_maf_fd produce and
+ *                  stream the text in batches of whole lines of at most this many bytes
+ *                  (always at least one line).  The text does not depend on it.
  * (Option ids 1, 4, 5 and 11 -- subtree-region, heavy-path-chain and level-band schedules,
  * tail records overlapped with the pre-order levels -- were measured slower than, or no
  * faster than, the level kernels on MI355X and removed.) */
@@ -162,6 +165,7 @@ int pm_set_stream(pm_ctx* ctx, void* hip_stream);
 #define PM_OPT_CLUSTER 17
 #define PM_OPT_TAIL_PACK 18
 #define PM_OPT_VCF_BATCH_BYTES 19
+#define PM_OPT_MAF_BATCH_BYTES 20
 int pm_set_option(pm_ctx* ctx, int option, int64_t value);
 /* Accumulate per-kernel-class device time with HIP events (see pm_kernel_times). */
 int pm_set_profiling(pm_ctx* ctx, int enable);
@@ -414,6 +418,37 @@ int pm_vcf(pm_ctx* ctx, const pm_panmat* panmat, const char* reference, char** t
            int64_t* skipped);
 int pm_vcf_fd(pm_ctx* ctx, const pm_panmat* panmat, const char* reference, int fd, int64_t* length,
               int64_t* skipped);
+/* Drop-in for Tree::printMAF(fout) (src/maf.cpp:68-188; the --maf command,
+ * src/panmanUtils.cpp:741-763): the multiple whole-genome alignment, block by block.  Tips are
+ * the leaves in node-id order (the order pm_fasta prints its records).
+ *   text(t, b)  block b's canonical, forward row of tip t (per main position its gap slots,
+ *               then its main character, the end sentinel last) with every 'x' printed as '-',
+ *               as getBlockSequenceFromReference builds it (src/panman.cpp:3070-3261); a
+ *               reverse strand only changes the strand field.
+ *   size(t, b)  the characters of text(t, b) that are not '-' (stripGaps).
+ *   start(t, b) the sum of size(t, b') over the blocks b' the tip holds that come before b in
+ *               the tip's print order (block ids rotated left to the rotation_index-th held
+ *               block, then reversed when sequence_inverted: getSequenceFromReference(rotate =
+ *               true), src/panman.cpp:4974-4999); with circular_offset >= 0 the offset is
+ *               subtracted and, if the result is negative, srcSize added once (maf.cpp:125-136:
+ *               no modulo, so an offset above srcSize prints a negative start).
+ *   srcSize(t)  the sum of size(t, b) over the blocks the tip holds.
+ * Text: "##maf version=1\n"; then one paragraph per group of blocks with equal consensusSeq
+ * words (the raw block_seq words), groups in lexicographic order over unsigned words with a
+ * proper prefix first (std::map<std::vector<uint32_t>, ...>), blocks of a group in block-list
+ * order: "a\n", per block and per tip that holds it
+ * "s\t<name>\t<start>\t<size>\t<+ or ->\t<srcSize>\t<text>\n", then "\n" -- also for a group
+ * no tip holds.  Inside a block the lines are in tip order (the reference iterates a
+ * concurrent map there: scheduler-defined).
+ * Sizes, starts, line lengths and the text are computed on the GPU from the replayed rows
+ * (profiling class 3), the text in batches of whole lines (PM_OPT_MAF_BATCH_BYTES) streamed
+ * through the pinned download slots.  Phase log: maf.*.
+ * `*text` is malloc'd (release with pm_free); pm_maf_fd writes to `fd` instead (`length`
+ * nullable).  Errors: a PanMAT with a nucleotide mutation on a secondary block:
+ * PM_ERR_UNSUPPORTED (getBlockSequenceFromReference skips it where the replay applies it to the
+ * primary block); no tip: PM_ERR_ARG; a failed write: PM_ERR_ARG (errno kept), as pm_fasta_fd. */
+int pm_maf(pm_ctx* ctx, const pm_panmat* panmat, char** text, int64_t* length);
+int pm_maf_fd(pm_ctx* ctx, const pm_panmat* panmat, int fd, int64_t* length);
 /* Canonical aligned columns per leaf of the prepared PanMAT (gap slots before each main
  * position, block sentinels included) and the number of leaves. */
 int pm_replay_shape(pm_ctx* ctx, int64_t* leaves, int64_t* columns, int64_t* edits);

@@ -135,6 +135,17 @@ class Tree {
         pm_free(text);
     }
 
+    // Tree::printMAF(fout) (src/maf.cpp:68-188); inside a block the lines are in tip order.
+    void printMAF(std::ostream& fout) const {
+        detail::Ctx ctx(device_);
+        pm_panmat v = view();
+        char* text = nullptr;
+        int64_t len = 0;
+        ctx.check(pm_maf(ctx.c, &v, &text, &len), "pm_maf");
+        fout.write(text, (std::streamsize)len);
+        pm_free(text);
+    }
+
     // Tree::printSummary(out) (src/summary.cpp:257-273); the block lines go to std::cout as
     // getBlockMutationsParallel prints them (:203-250).
     void printSummary(std::ostream& out) const {

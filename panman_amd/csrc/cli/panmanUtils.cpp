@@ -1,6 +1,6 @@
 // panmanUtils-compatible command line for the GPU path (src/panmanUtils.cpp:128-182 option
 // table, :1302-1325 PanMAN load, :1409-1465 MSA build, :271-299 writePanMAN, :385-415 and
-// :458-490 FASTA / aligned FASTA, :766-786 Newick).  Only the commands on the accelerated
+// :458-490 FASTA / aligned FASTA, :741-763 MAF, :766-786 Newick).  Only the commands on the accelerated
 // path are implemented; any other reference command is rejected with a message.
 #include <fcntl.h>
 #include <unistd.h>
@@ -51,8 +51,9 @@ const Spec kSpecs[] = {
     {"newick", 't', false, "Print newick string of all trees in a PanMAN"},
     {"fasta", 'f', false, "Print tip sequences (FASTA format)"},
     {"fasta-aligned", 'm', false, "Print MSA of sequences for each PanMAT in a PanMAN (FASTA format)"},
+    {"maf", 'w', false, "Print m-WGA for each PanMAT in a PanMAN (MAF format)"},
     {"reroot", 'r', false, "Reroot a PanMAT in a PanMAN based on the input sequence id (--reference)"},
-    {"treeID", 'd', true, "Tree ID, required for --reroot"},
+    {"treeID", 'd', true, "Tree ID, required for --reroot; the tree of --maf (default 0)"},
     {"protobuf2capnp", 0, false, "Converts a Google Protobuf PanMAN (-I) to a Cap'n Proto PanMAN (-o)"},
     {"low-mem-mode", 0, false, "Build with the Sankoff driver (the reference's batched low-memory mode)"},
     {"reference", 'n', true, "Identifier of reference sequence for PanMAN construction (optional) or reroot (required)"},
@@ -65,7 +66,7 @@ const Spec kSpecs[] = {
 
 // Reference commands outside the accelerated path: recognised so the error is explicit.
 const char* const kOther[] = {"input-gfa", "impute", "create-network", "printTips",
-                              "subnet", "vcf", "gfa", "maf", "annotate",
+                              "subnet", "vcf", "gfa", "annotate",
                               "aa-translation", "extended-newick", "printMutations", "acr", "index",
                               "toUsher"};
 
@@ -262,6 +263,48 @@ int reroot(const Options& o, const pm_panman* file, int device) {
     return 0;
 }
 
+// -I in.panman --maf [--treeID k] [-o out] (src/panmanUtils.cpp:741-763): Tree::printMAF of one
+// tree to stdout or ./info/<out>.maf, streamed from the device (pm_maf_fd).
+int maf(const Options& o, const pm_panman* file, int device) {
+    const int tree_id = o.has("treeID") ? std::atoi(o.get("treeID").c_str()) : 0;
+    if (tree_id < 0 || tree_id >= pm_panman_tree_count(file)) {
+        print_error("TreeID out of range");
+        return 1;
+    }
+    pm_ctx* ctx = nullptr;
+    if (pm_create(device, &ctx) != PM_OK) {
+        print_error("no HIP device");
+        return 1;
+    }
+    int fd = 1;
+    const bool to_file = o.has("output-file");
+    if (to_file) {
+        const std::string p = "./info/" + o.get("output-file") + ".maf";
+        fd = ::open(p.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (fd < 0) {
+            print_error("cannot write " + p);
+            pm_destroy(ctx);
+            return 1;
+        }
+    } else {
+        std::cout.flush();
+        std::fflush(stdout);
+    }
+    int status = 0;
+    pm_panmat view;
+    int64_t len = 0;
+    const auto t0 = Clock::now();
+    if (pm_panman_tree(file, tree_id, &view) != PM_OK || pm_maf_fd(ctx, &view, fd, &len) != PM_OK) {
+        print_error(pm_last_error(ctx));
+        status = 1;
+    }
+    const long long t = ns_since(t0);
+    if (to_file && ::close(fd) != 0) status = 1;
+    pm_destroy(ctx);
+    if (status == 0) std::cout << "\nMAF execution time: " << t << " nanoseconds\n";
+    return status;
+}
+
 // -P pangraph.json -N tree.nwk -o out [-n ref] (src/panmanUtils.cpp:1364-1407)
 int build_from_pangraph(const Options& o, int device) {
     if (!o.has("input-newick")) {
@@ -380,6 +423,11 @@ int from_panman(const Options& o, const std::vector<int>& devices) {
     int status = 0;
     if (o.has("reroot")) {   // src/panmanUtils.cpp:855-892, then writePanMAN
         status = reroot(o, file, device);
+        pm_panman_free(file);
+        return status;
+    }
+    if (o.has("maf")) {
+        status = maf(o, file, device);
         pm_panman_free(file);
         return status;
     }

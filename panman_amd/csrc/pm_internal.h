@@ -387,6 +387,7 @@ struct pm_ctx {
     size_t rows_cap = 0;
 
     int64_t vcf_batch_bytes = (int64_t)1 << 30;   // pm_vcf: genotype text per device batch (PM_OPT_VCF_BATCH_BYTES)
+    int64_t maf_batch_bytes = (int64_t)1 << 30;   // pm_maf: text per device batch of whole lines (PM_OPT_MAF_BATCH_BYTES)
 };
 
 namespace pm {
@@ -605,6 +606,54 @@ struct VcfTextArgs {
 hipError_t launch_vcf_text_count(pm_ctx* c, const VcfTextArgs& t);
 hipError_t launch_vcf_text_write(pm_ctx* c, const VcfTextArgs& t);
 hipError_t warm_vcf();
+// MAF extraction (pm_maf.hip; Tree::printMAF, src/maf.cpp:68-188) over the replayed rows:
+// row(t, b) = rows[t][blk_lo[b] .. blk_hi[b]).  Lines are addressed as entries
+// rank * tips + tip, rank = the block's place in the printed (group, block-list) order.
+constexpr int32_t kMafChunk = 4096;      // body bytes per workgroup of k_maf_write
+// workgroups per line of a block `width` columns wide (a line without a body still has its prefix)
+__host__ __device__ inline int32_t maf_chunks(int64_t width) {
+    return width > kMafChunk ? (int32_t)((width + kMafChunk - 1) / kMafChunk) : 1;
+}
+constexpr int32_t kMafHeld = 1, kMafForward = 2;      // MafArgs::held bits
+constexpr int32_t kMafOpens = 1, kMafCloses = 2;      // MafArgs::rank_fold bits
+struct MafArgs {
+    const char* rows;
+    int64_t row_stride;
+    int32_t tips, blocks;          // blocks: ids 0..max_id
+    const int64_t* blk_lo;         // [blocks]
+    const int64_t* blk_hi;
+    const uint8_t* held;           // [tips][blocks] kMafHeld | kMafForward
+    const int32_t* order;          // [tips][blocks] block ids in the tip's print order
+    const int32_t* circular;       // [tips] circular offset, < 0: none
+    int32_t* size;                 // [tips][blocks] ungapped characters (0 when not held)
+    int32_t* start;                // [tips][blocks]
+    int32_t* src_size;             // [tips]
+    int32_t ranks;
+    const int32_t* rank_blk;       // [ranks] block id
+    const uint8_t* rank_fold;      // [ranks] kMafOpens: "a\n" before its first entry; kMafCloses: "\n" after its last
+    const int64_t* name_off;       // [tips + 1] into names
+    const char* names;
+    int64_t* line_len;             // [ranks * tips] bytes of each entry, folds included
+};
+// size[t][b] for the blocks cls_blk[0 .. n) of one width class: G lanes per (tip, block) item
+// (G = 4: at most kMafNarrow4 columns, 16: at most kMafNarrow16, 64: any width)
+constexpr int64_t kMafNarrow4 = 49, kMafNarrow16 = 241;
+hipError_t launch_maf_size(pm_ctx* c, const MafArgs& a, const int32_t* cls_blk, int32_t n, int lanes);
+hipError_t launch_maf_start(pm_ctx* c, const MafArgs& a);
+hipError_t launch_maf_line_len(pm_ctx* c, const MafArgs& a);
+// out[0 .. n) = exclusive scan of in[0 .. n)
+hipError_t maf_scan(pm_ctx* c, const int64_t* in, int64_t* out, int64_t n);
+// The text of the entries [e0, e1) at text + line_off[e - e0]; wg_off[k] = first workgroup of
+// rank rank0 + k's entries inside the batch (its tips x its chunks), wg_off[nr] = the grid.
+struct MafBatch {
+    int64_t e0, e1;
+    int32_t rank0, nr;
+    const int32_t* wg_off;         // [nr + 1]
+    const int64_t* line_off;       // [e1 - e0]
+    char* text;
+};
+hipError_t launch_maf_write(pm_ctx* c, const MafArgs& a, const MafBatch& b, int32_t workgroups);
+hipError_t warm_maf();
 // rows[leaf][c0 .. c0+n) chars -> packed codes out[leaf][(n+1)/2] ('-', 'x' -> 0)
 hipError_t launch_rows_to_codes(pm_ctx* c, const char* rows, int64_t row_stride, int32_t leaves, int64_t c0,
                                 int64_t n, uint8_t* out, int64_t out_stride);

@@ -633,6 +633,23 @@ void free_replay(pm_ctx* c) {
 }  // namespace pm
 
 namespace pm {
+// A leaf's block print order (getSequenceFromReference(rotate = true), src/panman.cpp:4974-4999).
+void print_order(const ReplayState& r, int32_t li, std::vector<int32_t>& order) {
+    const int32_t M = r.max_id + 1;
+    order.resize(M);
+    for (int32_t i = 0; i < M; ++i) order[i] = i;
+    const auto& ex = r.exists[li];
+    if (r.rotation[li] != 0) {   // rotate to the rotationIndexes-th existing block (:1950-1964)
+        int32_t ctr = -1, at = 0;
+        for (int32_t i = 0; i < M; ++i) {
+            if (ex[i]) ++ctr;
+            if (ctr == r.rotation[li]) { at = i; break; }
+        }
+        std::rotate(order.begin(), order.begin() + at, order.end());
+    }
+    if (r.inverted[li]) std::reverse(order.begin(), order.end());
+}
+
 // The FASTA text of the replayed rows in the context's device text buffer (c->text_buf),
 // `total` bytes; `clock` carries on into the caller's download phase.  row_base / row_len
 // (nullable): per leaf the text offset of its first sequence character and its line length.
@@ -649,17 +666,8 @@ int format_device(pm_ctx* c, int aligned, int64_t& total, PhaseClock& clock, std
     host_parallel_for((L + LB - 1) / LB, [&](int task) {
     std::vector<int32_t> order(M);
     for (int32_t li = task * LB; li < std::min(L, (task + 1) * LB); ++li) {
-        for (int32_t i = 0; i < M; ++i) order[i] = i;
+        print_order(r, li, order);
         const auto& ex = r.exists[li];
-        if (r.rotation[li] != 0) {   // rotate to the rotationIndexes-th existing block (:1950-1964)
-            int32_t ctr = -1, at = 0;
-            for (int32_t i = 0; i < M; ++i) {
-                if (ex[i]) ++ctr;
-                if (ctr == r.rotation[li]) { at = i; break; }
-            }
-            std::rotate(order.begin(), order.begin() + at, order.end());
-        }
-        if (r.inverted[li]) std::reverse(order.begin(), order.end());
         for (int32_t i = 0; i < M; ++i) {
             const int32_t id = order[i];
             FmtSeg& sg = seg[(size_t)li * M + i];

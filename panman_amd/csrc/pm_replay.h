@@ -79,6 +79,11 @@ struct ReplayHost {
 int replay_flatten(const pm_panmat* p, ReplayState& r, ReplayHost& h, int64_t leaf_begin, int64_t leaf_end,
                    std::string& err_msg);
 
+// Block ids 0..max_id in the order leaf `li` prints them: rotated left to its
+// rotation-index-th existing block, then reversed when the sequence is inverted
+// (getSequenceFromReference(rotate = true), src/panman.cpp:4974-4999).  Shared by the FASTA
+// formatter and the MAF driver.
+void print_order(const ReplayState& r, int32_t li, std::vector<int32_t>& order);
 // prepare + replay of every leaf (pm_fasta's first half); the rows stay in c->replay.
 int fasta_replay(pm_ctx* c, const pm_panmat* p);
 // The FASTA text of the replayed rows in c->text_buf (`total` bytes).  row_base / row_len
