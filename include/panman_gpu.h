@@ -148,6 +148,9 @@ int pm_set_stream(pm_ctx* ctx, void* hip_stream);
  *   PM_OPT_MAF_BATCH_BYTES (default 1 GiB, at least 4096): pm_maf / pm_maf_fd produce and
  *                  stream the text in batches of whole lines of at most this many bytes
  *                  (always at least one line).  The text does not depend on it.
+ *   PM_OPT_GFA_BATCH_BYTES (default 1 GiB, at least 4096): pm_gfa / pm_gfa_fd produce and
+ *                  stream the "P" lines in batches of whole lines of at most this many bytes
+ *                  (always at least one line).  The text does not depend on it.
  * (Option ids 1, 4, 5 and 11 -- subtree-region, heavy-path-chain and level-band schedules,
  * tail records overlapped with the pre-order levels -- were measured slower than, or no
  * faster than, the level kernels on MI355X and removed.) */
@@ -166,6 +169,7 @@ int pm_set_stream(pm_ctx* ctx, void* hip_stream);
 #define PM_OPT_TAIL_PACK 18
 #define PM_OPT_VCF_BATCH_BYTES 19
 #define PM_OPT_MAF_BATCH_BYTES 20
+#define PM_OPT_GFA_BATCH_BYTES 21
 int pm_set_option(pm_ctx* ctx, int option, int64_t value);
 /* Accumulate per-kernel-class device time with HIP events (see pm_kernel_times). */
 int pm_set_profiling(pm_ctx* ctx, int enable);
@@ -449,6 +453,49 @@ int pm_vcf_fd(pm_ctx* ctx, const pm_panmat* panmat, const char* reference, int f
  * primary block); no tip: PM_ERR_ARG; a failed write: PM_ERR_ARG (errno kept), as pm_fasta_fd. */
 int pm_maf(pm_ctx* ctx, const pm_panmat* panmat, char** text, int64_t* length);
 int pm_maf_fd(pm_ctx* ctx, const pm_panmat* panmat, int fd, int64_t* length);
+/* Drop-in for Tree::convertToGFA(fout) (src/gfa.cpp:3-500; the --gfa command,
+ * src/panmanUtils.cpp:699-732): the tips as paths through a sequence graph.  Tips are the leaves
+ * in node-id order.  The reference has two branches.
+ * A. No node carries a nucleotide mutation (gfa.cpp:13-118), a graph of whole blocks:
+ *   "S\t<id>\t<text>\n" per block, id = the rank from 0 of its primary id, text = its
+ *   consensusSeq words, each decoded up to its first code 0 -- also for a block no tip holds;
+ *   a tip holds a block when the last block mutation of it on the tip's path is an insertion
+ *   (anything else, an inversion included, clears it; no strands here);
+ *   "L\t<a>\t+\t<b>\t+\t0M\n" per distinct pair of blocks consecutive in a tip's path (the held
+ *   blocks in id order), pairs in ascending (from, to) order;
+ *   "P\t<name>\t<a>+,<b>+\t*\n" per tip, in tip order.  No "H" line.  (A held id that is no
+ *   block's prints as 0, as the reference's map lookup does.)
+ * B. Otherwise (gfa.cpp:119-499), a graph of 32-column chunks of the canonical rows
+ *   rows[tip][blk_lo .. blk_hi) of getSequenceFromReference(rotate = false): rotation, sequence
+ *   inversion and circular offset play no part.
+ *   chunks   of a forward block: 32 columns each from the block's first column, the last one
+ *            shorter; of a reverse block: 32 columns each from the block's last column down, the
+ *            short one at the block's beginning, walked from the last chunk of the row to the
+ *            first and read in canonical order (not complemented).
+ *   node     (start, string): string = the chunk without '-' and 'x' (an empty one makes no node
+ *            and no path step); start = the chunk's first column as (block, position, gap slot)
+ *            on the forward strand, its lowest column as (-block - 1, position, -1) or
+ *            (-block, position, gap slot) on the reverse strand -- so block 0's reverse gap-slot
+ *            starts collide with forward starts, as they do in the reference.
+ *   ids      a new node gets the next id from 0 and the strand of the tip that made it.  Defined
+ *            schedule: tips in order, each completely before the next; blocks ascending; chunks
+ *            in walk order.  (The reference runs the tips under tbb::parallel_for_each.)
+ *   Then the reference's chain compaction, duplicate removal and renumbering (gfa.cpp:311-472),
+ *   restated literally on the host over the integer ids, tip names compared by their bytes.
+ *   Text: "H\tVN:Z:1.1\n"; "S\t<id>\t<text>\n" per final node; "L\t<a>\t<+|->\t<b>\t<+|->\t0M\n"
+ *   in the edge set's order; "P\t<name>\t<id><+|->,...\t*\n" per tip in tip order ("P\t<name>\t\t*\n"
+ *   for a tip without a step; the reference iterates a concurrent map here).
+ * Chunk keys, the exact unique over them (radix sort of the whole keys, neighbours compared in
+ * full), the ids and the "P" lines are computed on the GPU (profiling class 3), the "P" lines in
+ * batches of whole lines (PM_OPT_GFA_BATCH_BYTES) streamed through the pinned download slots;
+ * "H", "S" and "L" come from the host.  Phase log: gfa.*.
+ * `*text` is malloc'd (release with pm_free); pm_gfa_fd writes to `fd` instead (`length`
+ * nullable).  Errors: a nucleotide mutation on a secondary block: PM_ERR_UNSUPPORTED (as pm_maf);
+ * no tip: PM_ERR_ARG; in branch A a block mutation's id >= num_blocks + 1: PM_ERR_ARG (the
+ * reference indexes out of range); rows of 2^31 columns or more, or 2^31 path steps or more:
+ * PM_ERR_UNSUPPORTED; a failed write: PM_ERR_ARG (errno kept), as pm_fasta_fd. */
+int pm_gfa(pm_ctx* ctx, const pm_panmat* panmat, char** text, int64_t* length);
+int pm_gfa_fd(pm_ctx* ctx, const pm_panmat* panmat, int fd, int64_t* length);
 /* Canonical aligned columns per leaf of the prepared PanMAT (gap slots before each main
  * position, block sentinels included) and the number of leaves. */
 int pm_replay_shape(pm_ctx* ctx, int64_t* leaves, int64_t* columns, int64_t* edits);

@@ -146,6 +146,18 @@ class Tree {
         pm_free(text);
     }
 
+    // Tree::convertToGFA(fout) (src/gfa.cpp:3-500); node ids as if the tips ran one after the
+    // other in tip order, the "P" lines in tip order.
+    void convertToGFA(std::ostream& fout) const {
+        detail::Ctx ctx(device_);
+        pm_panmat v = view();
+        char* text = nullptr;
+        int64_t len = 0;
+        ctx.check(pm_gfa(ctx.c, &v, &text, &len), "pm_gfa");
+        fout.write(text, (std::streamsize)len);
+        pm_free(text);
+    }
+
     // Tree::printSummary(out) (src/summary.cpp:257-273); the block lines go to std::cout as
     // getBlockMutationsParallel prints them (:203-250).
     void printSummary(std::ostream& out) const {

@@ -1,6 +1,6 @@
 // panmanUtils-compatible command line for the GPU path (src/panmanUtils.cpp:128-182 option
 // table, :1302-1325 PanMAN load, :1409-1465 MSA build, :271-299 writePanMAN, :385-415 and
-// :458-490 FASTA / aligned FASTA, :741-763 MAF, :766-786 Newick).  Only the commands on the accelerated
+// :458-490 FASTA / aligned FASTA, :699-732 GFA, :741-763 MAF, :766-786 Newick).  Only the commands on the accelerated
 // path are implemented; any other reference command is rejected with a message.
 #include <fcntl.h>
 #include <unistd.h>
@@ -52,8 +52,9 @@ const Spec kSpecs[] = {
     {"fasta", 'f', false, "Print tip sequences (FASTA format)"},
     {"fasta-aligned", 'm', false, "Print MSA of sequences for each PanMAT in a PanMAN (FASTA format)"},
     {"maf", 'w', false, "Print m-WGA for each PanMAT in a PanMAN (MAF format)"},
+    {"gfa", 'g', false, "Convert any PanMAT in a PanMAN to a GFA file"},
     {"reroot", 'r', false, "Reroot a PanMAT in a PanMAN based on the input sequence id (--reference)"},
-    {"treeID", 'd', true, "Tree ID, required for --reroot; the tree of --maf (default 0)"},
+    {"treeID", 'd', true, "Tree ID, required for --reroot; the tree of --maf and --gfa (default 0)"},
     {"protobuf2capnp", 0, false, "Converts a Google Protobuf PanMAN (-I) to a Cap'n Proto PanMAN (-o)"},
     {"low-mem-mode", 0, false, "Build with the Sankoff driver (the reference's batched low-memory mode)"},
     {"reference", 'n', true, "Identifier of reference sequence for PanMAN construction (optional) or reroot (required)"},
@@ -66,7 +67,7 @@ const Spec kSpecs[] = {
 
 // Reference commands outside the accelerated path: recognised so the error is explicit.
 const char* const kOther[] = {"input-gfa", "impute", "create-network", "printTips",
-                              "subnet", "vcf", "gfa", "annotate",
+                              "subnet", "vcf", "annotate",
                               "aa-translation", "extended-newick", "printMutations", "acr", "index",
                               "toUsher"};
 
@@ -265,7 +266,10 @@ int reroot(const Options& o, const pm_panman* file, int device) {
 
 // -I in.panman --maf [--treeID k] [-o out] (src/panmanUtils.cpp:741-763): Tree::printMAF of one
 // tree to stdout or ./info/<out>.maf, streamed from the device (pm_maf_fd).
-int maf(const Options& o, const pm_panman* file, int device) {
+// -I in.panman --gfa [--treeID k] [-o out] (src/panmanUtils.cpp:699-732): Tree::convertToGFA of
+// one tree to stdout or ./info/<out>.gfa (pm_gfa_fd).
+int one_tree_text(const Options& o, const pm_panman* file, int device, const char* ext,
+                  int (*extract)(pm_ctx*, const pm_panmat*, int, int64_t*), const char* time_line) {
     const int tree_id = o.has("treeID") ? std::atoi(o.get("treeID").c_str()) : 0;
     if (tree_id < 0 || tree_id >= pm_panman_tree_count(file)) {
         print_error("TreeID out of range");
@@ -279,7 +283,7 @@ int maf(const Options& o, const pm_panman* file, int device) {
     int fd = 1;
     const bool to_file = o.has("output-file");
     if (to_file) {
-        const std::string p = "./info/" + o.get("output-file") + ".maf";
+        const std::string p = "./info/" + o.get("output-file") + ext;
         fd = ::open(p.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
         if (fd < 0) {
             print_error("cannot write " + p);
@@ -294,14 +298,14 @@ int maf(const Options& o, const pm_panman* file, int device) {
     pm_panmat view;
     int64_t len = 0;
     const auto t0 = Clock::now();
-    if (pm_panman_tree(file, tree_id, &view) != PM_OK || pm_maf_fd(ctx, &view, fd, &len) != PM_OK) {
+    if (pm_panman_tree(file, tree_id, &view) != PM_OK || extract(ctx, &view, fd, &len) != PM_OK) {
         print_error(pm_last_error(ctx));
         status = 1;
     }
     const long long t = ns_since(t0);
     if (to_file && ::close(fd) != 0) status = 1;
     pm_destroy(ctx);
-    if (status == 0) std::cout << "\nMAF execution time: " << t << " nanoseconds\n";
+    if (status == 0) std::cout << time_line << t << " nanoseconds\n";
     return status;
 }
 
@@ -427,7 +431,12 @@ int from_panman(const Options& o, const std::vector<int>& devices) {
         return status;
     }
     if (o.has("maf")) {
-        status = maf(o, file, device);
+        status = one_tree_text(o, file, device, ".maf", pm_maf_fd, "\nMAF execution time: ");
+        pm_panman_free(file);
+        return status;
+    }
+    if (o.has("gfa")) {
+        status = one_tree_text(o, file, device, ".gfa", pm_gfa_fd, "GFA generation time: ");
         pm_panman_free(file);
         return status;
     }

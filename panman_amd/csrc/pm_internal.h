@@ -388,6 +388,7 @@ struct pm_ctx {
 
     int64_t vcf_batch_bytes = (int64_t)1 << 30;   // pm_vcf: genotype text per device batch (PM_OPT_VCF_BATCH_BYTES)
     int64_t maf_batch_bytes = (int64_t)1 << 30;   // pm_maf: text per device batch of whole lines (PM_OPT_MAF_BATCH_BYTES)
+    int64_t gfa_batch_bytes = (int64_t)1 << 30;   // pm_gfa: text per device batch of whole P lines (PM_OPT_GFA_BATCH_BYTES)
 };
 
 namespace pm {
@@ -654,6 +655,76 @@ struct MafBatch {
 };
 hipError_t launch_maf_write(pm_ctx* c, const MafArgs& a, const MafBatch& b, int32_t workgroups);
 hipError_t warm_maf();
+// GFA extraction (pm_gfa.hip; Tree::convertToGFA, src/gfa.cpp:3-500) over the replayed rows.
+// A tip's walk is cut into items (tip, block, chunk): item = tip * chunks + chunk_off[block] + c,
+// which is the schedule order (tips in order, blocks ascending, chunks in walk order).  An item
+// of a held block whose columns are not all '-' / 'x' is a path step.
+constexpr int32_t kGfaNode = 32;   // columns per chunk (node_len, gfa.cpp:120)
+__host__ __device__ inline int32_t gfa_chunks(int64_t width) { return (int32_t)((width + kGfaNode - 1) / kGfaNode); }
+constexpr uint32_t kGfaReverseStart = 0x80000000u;   // start code: a reverse-strand start tuple
+struct GfaArgs {
+    const char* rows;
+    int64_t row_stride;
+    int32_t tips, blocks;          // blocks: ids 0..max_id
+    const int64_t* blk_lo;         // [blocks]
+    const int64_t* blk_hi;
+    const uint8_t* held;           // [tips][blocks] kMafHeld | kMafForward
+    int32_t chunks;                // chunks of all blocks together (items per tip)
+    const int32_t* chunk_off;      // [blocks + 1] first chunk of a block
+    const int32_t* chunk_blk;      // [chunks] the block of a chunk
+    const uint32_t* start_code;    // [2][chunks] forward, reverse: separates the start tuples
+    int64_t items;                 // tips * chunks
+    uint64_t* key;                 // [3][items] (start code << 32 | length), string bits 127..64, 63..0
+    int64_t* flag;                 // [items] 1: a step
+};
+hipError_t launch_gfa_chunk(pm_ctx* c, const GfaArgs& a);
+// The steps: items with a set flag, numbered by `scan` (the exclusive scan of the flags).
+struct GfaSteps {
+    int64_t steps;
+    uint64_t* key;                 // [3][steps]
+    int32_t* tip;                  // [steps]
+    uint8_t* forward;              // [steps] the path strand
+    int32_t* tip_off;              // [tips + 1] first step of a tip
+    int32_t* id;                   // [steps] node id: the rank of the node's first step
+};
+hipError_t launch_gfa_compact(pm_ctx* c, const GfaArgs& a, const int64_t* scan, const GfaSteps& s);
+// perm <- the steps sorted by the whole key, stable (equal keys stay in step order); scratch
+// holds 4 x steps 64-bit words
+hipError_t gfa_sort(pm_ctx* c, const GfaSteps& s, uint32_t* perm, uint64_t* scratch);
+// head[i] = 1 where the key at perm[i] differs from its left neighbour's; creator[perm[i]] = 1 there
+hipError_t launch_gfa_heads(pm_ctx* c, const GfaSteps& s, const uint32_t* perm, int64_t* head, int64_t* creator);
+// run_first[r] = first (earliest) step of the r-th run; hscan / cscan: scans of head / creator
+hipError_t launch_gfa_runs(pm_ctx* c, const GfaSteps& s, const uint32_t* perm, const int64_t* head, const int64_t* hscan,
+                           int32_t* run_first);
+// id[step] = cscan[its run's first step]; per node its key (length, string) and creator strand
+struct GfaNodes {
+    uint64_t* key;                 // [3][nodes]
+    uint8_t* forward;              // [nodes]
+    int64_t nodes;
+};
+hipError_t launch_gfa_ids(pm_ctx* c, const GfaSteps& s, const uint32_t* perm, const int64_t* head, const int64_t* hscan,
+                          const int32_t* run_first, const int64_t* cscan, const GfaNodes& n);
+// "P" lines: printed[2 * id + forward] is the step's printed id, -1 when the step is dropped.
+struct GfaText {
+    int64_t steps;
+    int32_t tips;
+    const int32_t* id;             // [steps]
+    const uint8_t* forward;        // [steps]
+    const int32_t* tip;            // [steps]
+    const int32_t* tip_off;        // [tips + 1]
+    const int32_t* printed;
+    int64_t* step_len;             // [steps + 1] bytes of a step with its comma (0: dropped; [steps] = 0)
+    const int64_t* step_off;       // [steps + 1] their exclusive scan
+    const int64_t* name_off;       // [tips + 1] into names
+    const char* names;
+    int64_t* line_len;             // [tips]
+};
+hipError_t launch_gfa_step_len(pm_ctx* c, const GfaText& t);
+hipError_t launch_gfa_line_len(pm_ctx* c, const GfaText& t);
+// the lines of tips [t0, t1) at text + line_off[t - t0]; batch_steps = tip_off[t1] - tip_off[t0]
+hipError_t launch_gfa_write(pm_ctx* c, const GfaText& t, int32_t t0, int32_t t1, const int64_t* line_off, char* text,
+                            int64_t batch_steps);
+hipError_t warm_gfa();
 // rows[leaf][c0 .. c0+n) chars -> packed codes out[leaf][(n+1)/2] ('-', 'x' -> 0)
 hipError_t launch_rows_to_codes(pm_ctx* c, const char* rows, int64_t row_stride, int32_t leaves, int64_t c0,
                                 int64_t n, uint8_t* out, int64_t out_stride);
