@@ -118,6 +118,16 @@ int pm_set_stream(pm_ctx* ctx, void* hip_stream);
  *                  waves: a launch the chip holds at once is no faster packed.  A value >= 2
  *                  sets that threshold, -1 packs at any size, 0 = one wave per item.  Results
  *                  identical.  Sankoff and PM_OPT_SUB_DOWN runs do not use it.
+ *   PM_OPT_DOWN_PACK (default 1): Fitch, every leaf present -- a pre-order level that is a
+ *                  launch of its own (no level group, no band, not the root's, not under
+ *                  PM_OPT_SUB_DOWN) and a dense range of nodes runs eight consecutive nodes per
+ *                  wave, the live (node, word) pairs of the eight -- the node's or its parent's
+ *                  word is complex, or a leaf / leaf-parent child is read there; every word
+ *                  under the root -- gathered into full waves, instead of one wave per (node,
+ *                  tile) with about one lane in seven busy -- when the level makes at least
+ *                  65536 (node, tile) waves.  A value >= 2 sets that threshold, -1 packs at any
+ *                  size, 0 = one wave per (node, tile).  Results identical.  Sankoff, block
+ *                  Fitch and inputs with absent leaves do not use it.
  *   PM_OPT_PLAIN_UP (default 1): Fitch / Sankoff, grouped subtree form -- a post-order launch's binary
  *                  nodes with no three- / four-leaf subtree child and nothing recomputed run in
  *                  a lean kernel (fewer registers, more waves in flight) before the rest, when
@@ -170,6 +180,7 @@ int pm_set_stream(pm_ctx* ctx, void* hip_stream);
 #define PM_OPT_VCF_BATCH_BYTES 19
 #define PM_OPT_MAF_BATCH_BYTES 20
 #define PM_OPT_GFA_BATCH_BYTES 21
+#define PM_OPT_DOWN_PACK 22
 int pm_set_option(pm_ctx* ctx, int option, int64_t value);
 /* Accumulate per-kernel-class device time with HIP events (see pm_kernel_times). */
 int pm_set_profiling(pm_ctx* ctx, int enable);
@@ -278,7 +289,11 @@ int pm_chunk_unpack(const uint64_t* all, int64_t per, int ranks, int64_t total_s
  * the pre-order's reads at 128-B line granularity (every line a load touches, as the memory
  * fetches them: tools/calib_fetch.hip) -- level kernels: descriptors + masks + own records,
  * parent finals, dirty-lane leaf words; tail: descriptors + masks, dirty-lane leaf words,
- * parent finals.  `n` >= 5.
+ * parent finals.  In the levels PM_OPT_DOWN_PACK packed, own simple codes and parent finals count
+ * at live lanes only, as the packed kernel reads them.  With n >= 31, out[20..30]: the live lanes
+ * of those levels' (node, tile) waves -- or, the option off, of the levels it would pack -- as
+ * waves counted, live lanes in total and a histogram of live lanes per wave (0, 1-8, 9-16, ..,
+ * 57-64).  `n` >= 5.
  * Synchronises the ctx stream. */
 int pm_design_bytes(pm_ctx* ctx, double* out, int n);
 /* FETCH_SIZE calibration for scattered reads: `lanes` threads each read 4 x 16 B, one 16-B

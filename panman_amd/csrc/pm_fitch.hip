@@ -915,6 +915,11 @@ hipError_t launch_fitch(pm_ctx* c, bool block) {
         }
     }
     const int D = cld ? 0 : (int)down_off.size() - 1;
+    // packed levels (PM_OPT_DOWN_PACK): ungrouped, non-band launches of k_down<Fitch, AP, DENSE>
+    const bool pack_form = !kCxCompact && !block && ap && !sub_down;
+    const int64_t down_pack_min = c->down_pack_min_waves != 0 ? c->down_pack_min_waves : kDownPackMinWaves;
+    int packed_levels = 0;
+    c->down_pack_ranges.clear();
     for (int d = 0; d < D; ++d) {
         if (c->narrow_max > 0 && down_off[d + 1] - down_off[d] <= c->narrow_max) {
             int d1 = d + 1;
@@ -976,6 +981,21 @@ hipError_t launch_fitch(pm_ctx* c, bool block) {
             d += g - 1;
             continue;
         }
+        // PM_OPT_DOWN_PACK: a large dense level of the lean all-present kernel, below the root's,
+        // in groups of kDownPack items per wave (k_down<.., G>)
+        const bool packs = pack_form && dense && d > 0 && (int64_t)dn.count * tiles >= down_pack_min;
+        if (packs) {   // (kept for pm_design_bytes: the levels the option takes, or would take)
+            c->down_pack_ranges.push_back(dn.dense_base);
+            c->down_pack_ranges.push_back(dn.count);
+        }
+        if (packs && c->down_pack) {
+            const dim3 grid = wave_grid((dn.count + kDownPack - 1) / kDownPack, tiles);
+            timer_begin(c, 1);
+            hipLaunchKernelGGL((k_down<Mode::kFitch, true, true, false, false, kDownPack>), grid, dim3(kBlock), 0, c->stream, dn);
+            timer_end(c, 1);
+            ++packed_levels;
+            continue;
+        }
         const dim3 grid = wave_grid(dn.count, tiles);
         timer_begin(c, 1);
         // (subtree form: the levels' descriptors omit S2 / S3 children, whose records come
@@ -989,6 +1009,8 @@ hipError_t launch_fitch(pm_ctx* c, bool block) {
         else hipLaunchKernelGGL((k_down<Mode::kFitch, false, false>), grid, dim3(kBlock), 0, c->stream, dn);
         timer_end(c, 1);
     }
+    phase_add("run.down_pack", packed_levels > 0 ? (double)kDownPack : 0.0);   // the group size the packed levels took (0: none packed)
+    phase_add("run.down_pack_launches", (double)packed_levels);
     // The tail (children beyond the second, S2 / S3 subtrees) needs only its parents'
     // finals: one flat launch after the levels.
     // (PM_OPT_SUB_DOWN: the S2 / S3 items, the first num_tail_s, were done by the levels)

@@ -310,6 +310,9 @@ struct pm_ctx {
     bool sub_down = false;            // Fitch subtree form: S2 / S3 records in their parent's pre-order wave (PM_OPT_SUB_DOWN)
     bool tail_pack = true;            // Fitch subtree form: the tail's S2 / S3 items in groups per wave, dirty words gathered into full waves (PM_OPT_TAIL_PACK)
     int64_t tail_pack_min_waves = 0;  // ... from this many (S item, tile) waves (0: kTailPackMinWaves, -1: always)
+    bool down_pack = true;            // Fitch, all leaves present: large dense pre-order levels in groups per wave, live words gathered into full waves (PM_OPT_DOWN_PACK)
+    int64_t down_pack_min_waves = 0;  // ... from this many (item, tile) waves (0: kDownPackMinWaves, -1: always)
+    std::vector<int32_t> down_pack_ranges;   // ... the last Fitch launch sequence's such levels, (first dense index, items) pairs -- taken, or with the option off the ones it would take
     bool plain_up = true;             // grouped subtree form: plain nodes in the lean post-order kernels (PM_OPT_PLAIN_UP)
     int64_t plain_min_waves = 0;      // ... from this many (node, tile) waves (0: kPlainMinWaves)
     bool cluster = true;              // Fitch subtree form: LDS-staged post-order sweeps above ht.cl.h0 (PM_OPT_CLUSTER)

@@ -1460,6 +1460,29 @@ __device__ __forceinline__ void kid_emit(const Args& a, Emit& em, int lane, cons
         emit_stream(a, em, lane, id2, valid & k.m1 & diff4(k.L1, F), site0, k.L1.x, k.L1.y, k.L1.z, k.L1.w, F);
 }
 
+// kid_emit where the child's kind, ids and site0 differ from lane to lane (packed levels): every
+// lane stages the three streams a leaf-parent has -- its own, then its leaves' -- with empty
+// masks where the lane's child has none (emit_stream's ballots need the whole wave).  A leaf
+// child is the second stream against the node's final; a materialised child stages nothing
+// (m0 = m1 = 0).  Fitch.
+template <class Args>
+__device__ __forceinline__ void kid_emit_lanes(const Args& a, Emit& em, int lane, int32_t enc, const uint4& L0, const uint4& L1,
+                                               uint32_t m0, uint32_t m1, uint32_t id0, uint32_t id1, uint32_t id2,
+                                               uint32_t valid, const uint32_t* Fn, uint32_t site0) {
+    const bool virt = enc >= 0 && (enc & kVirtualBit);
+    uint32_t low[4] = {0, 0, 0, 0}, have = 0, hit = 0;
+    virt_fold(L0, m0, Fn, low, have, hit);
+    virt_fold(L1, m1, Fn, low, have, hit);
+    if (!virt) hit = ~0u;   // (a leaf's records are against the node's final)
+    uint32_t F[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) F[j] = bsel(hit, Fn[j], low[j]);
+    const uint32_t self = have & valid & ((F[0] ^ Fn[0]) | (F[1] ^ Fn[1]) | (F[2] ^ Fn[2]) | (F[3] ^ Fn[3]));
+    emit_stream(a, em, lane, id0, self, site0, F[0], F[1], F[2], F[3], Fn);
+    emit_stream(a, em, lane, virt ? id1 : id0, valid & m0 & diff4(L0, F), site0, L0.x, L0.y, L0.z, L0.w, F);
+    emit_stream(a, em, lane, id2, valid & m1 & diff4(L1, F), site0, L1.x, L1.y, L1.z, L1.w, F);
+}
+
 // Where a complex lane's final goes: the record's simple area past the simple lanes' codes
 // (slots popc(s) .. popc(s) + popc(x) - 1 are never used by the set, x and s being
 // disjoint), so the set's complex planes stay intact after the node's pre-order step and a
@@ -1698,9 +1721,196 @@ __device__ __forceinline__ void down_node(const DownArgs& a, const NodeDesc& d, 
     emit_flush<M != Mode::kSankoff>(a, em, lane);
 }
 
+__device__ __forceinline__ uint32_t bits_below(uint64_t m, uint32_t l) {   // set bits of m below bit l (l per lane)
+    return (uint32_t)__builtin_popcountll(m & ((1ull << l) - 1ull));
+}
+
+// Packed levels (PM_OPT_DOWN_PACK; Fitch, every leaf present, dense levels): one wave = G
+// consecutive items of the level at one tile, their live (item, word) pairs gathered into full
+// waves as the packed tail gathers its dirty ones (tail_packed).  A lane of a node's own wave has
+// something to compute, store or emit only where it is live:
+//   live = x | px | (first child a leaf ? x : a leaf-parent ? word 6 : 0) | (second: word 7)
+// -- the node's complex lanes, its parent's, and the lanes its leaf-ish children are read at.
+// Elsewhere the parent's set is one code c at all 32 sites, so the node's (one-code) set is c,
+// its final is c (no record, and only complex lanes store a final) and its first two children
+// emit nothing (leaf_rule; words 6, 7).  Under the root every lane is live: the root's final
+// does not follow from its children's sets (lowest code, or forced).
+//   lane g < G loads item g's mask record and descriptor -- both addressed by the item index
+//   alone -- and behind the descriptor the node ids its records carry, and leaves them in LDS;
+//   each live lane l of item g writes g * 64 + l at slot prefix[g] + its rank;
+//   lane j of round r reads slot 64 r + j and through it its item's descriptor, masks and ids,
+//   issues the loads of down_node at that (item, word) -- own code, own complex planes at an x
+//   lane, the parent's final, the children's dirty words -- and goes on as down_node does.
+// Same addresses as the items' own waves, live lanes only.  Never the root's level (its wave
+// writes root_final and the root codes at every lane).
+#ifndef PM_DOWN_PACK
+#define PM_DOWN_PACK 8
+#endif
+// (five waves per SIMD: 92 VGPRs, no scratch; at six the round's loads -- 4 + 16 + 4 + 16
+// registers in flight together -- spill 14 VGPRs)
+#ifndef PM_DOWN_PACK_WAVES
+#define PM_DOWN_PACK_WAVES 5
+#endif
+constexpr int kDownPack = PM_DOWN_PACK;
+// ... from this many (item, tile) waves of the level's own launch (the packed tail's threshold)
+#ifndef PM_DOWN_PACK_MIN_WAVES
+#define PM_DOWN_PACK_MIN_WAVES 65536
+#endif
+constexpr int64_t kDownPackMinWaves = PM_DOWN_PACK_MIN_WAVES;
+// per item: {parent, c0, c1, node id}, the children's leaves {l00, l01, l10, l11}, the first
+// child's ids, the second's, {x, s}, {px, ps}, {k0, k1}
+constexpr int kDownInfoQuads = 7;
+
+template <int G>
+__device__ __forceinline__ void down_packed(const DownArgs& a, int32_t group, int tile, int lane, uint4* stage, uint4* info,
+                                            uint16_t* slots) {
+    // (reads the 16-plane complex lanes: a PM_CX_COMPACT build never launches it, launch_fitch)
+    constexpr int REC = kFitchRec;
+    const int32_t item0 = group * G;
+    const int32_t mine = item0 + lane;
+    const bool own = lane < G && mine < a.count;
+    uint64_t mx = 0, ms = 0, px = 0, ps = 0, k0 = 0, k1 = 0, live = 0;
+    int32_t parent = 0, c0 = 0, c1 = 0;
+    int32_t lf[4] = {-1, -1, -1, -1};
+    uint32_t node_id = 0, id0[3] = {0, 0, 0}, id1[3] = {0, 0, 0};
+    if (own) {
+        const int32_t n = a.dense_base + mine;
+        const uint64_t* q = a.cmask + kMaskWords * ((size_t)n * a.tiles + tile);
+        mx = q[0];
+        ms = q[1];
+        px = q[3];
+        ps = q[4];
+        const uint64_t q6 = q[6], q7 = q[7];
+        const uint4* dp = reinterpret_cast<const uint4*>(a.desc + mine);
+        const uint4 d0 = dp[0], d1 = dp[1], d2 = dp[2], d3 = dp[3];   // {node, parent, e0, e1}, {c0, c1, ..}, vl0, vl1
+        node_id = (uint32_t)a.internal_id[n];
+        parent = (int32_t)d0.y;
+        c0 = (int32_t)d1.x;
+        c1 = (int32_t)d0.w - (int32_t)d0.z > 1 ? (int32_t)d1.y : 0;   // (no second child: a materialised placeholder)
+        // a child's leaves to read, its ids, its dirty lanes (a materialised child: none)
+        auto kid = [&](int32_t enc, const uint4& vl, uint64_t kw, int32_t* l, uint32_t* id, uint64_t& k) {
+            if (enc < 0) {
+                l[0] = -enc - 1;
+                id[0] = (uint32_t)a.leaf_id[l[0]];
+                k = mx;
+            } else if (enc & kVirtualBit) {
+                l[0] = (int32_t)vl.x;
+                l[1] = (int32_t)vl.y;
+                id[0] = (uint32_t)a.internal_id[enc & kDenseMask];
+                id[1] = (uint32_t)a.leaf_id[l[0]];
+                if (l[1] >= 0) id[2] = (uint32_t)a.leaf_id[l[1]];
+                k = kw;
+            }
+        };
+        kid(c0, d2, q6, lf, id0, k0);
+        kid(c1, d3, q7, lf + 2, id1, k1);
+        live = parent == a.root_dense ? ~0ull : (mx | px | k0 | k1);
+    }
+    uint32_t T;
+    const uint32_t pre = wave_exclusive_scan((uint32_t)__builtin_popcountll(live), T);
+    if (T == 0) return;   // no live lane in the group
+    if (lane < G) {
+        uint4* w = info + lane * kDownInfoQuads;
+        w[0] = make_uint4((uint32_t)parent, (uint32_t)c0, (uint32_t)c1, node_id);
+        w[1] = make_uint4((uint32_t)lf[0], (uint32_t)lf[1], (uint32_t)lf[2], (uint32_t)lf[3]);
+        w[2] = make_uint4(id0[0], id0[1], id0[2], 0u);
+        w[3] = make_uint4(id1[0], id1[1], id1[2], 0u);
+        w[4] = make_uint4((uint32_t)mx, (uint32_t)(mx >> 32), (uint32_t)ms, (uint32_t)(ms >> 32));
+        w[5] = make_uint4((uint32_t)px, (uint32_t)(px >> 32), (uint32_t)ps, (uint32_t)(ps >> 32));
+        w[6] = make_uint4((uint32_t)k0, (uint32_t)(k0 >> 32), (uint32_t)k1, (uint32_t)(k1 >> 32));
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)live, g), hi = __builtin_amdgcn_readlane((uint32_t)(live >> 32), g);
+        const uint64_t m = (uint64_t)lo | ((uint64_t)hi << 32);   // (readlane returns int: widened unsigned)
+        const uint32_t p = __builtin_amdgcn_readlane(pre, g);
+        if ((m >> lane) & 1ull) slots[p + lanes_below(m)] = (uint16_t)(g * kWave + lane);
+    }
+    __builtin_amdgcn_wave_barrier();   // (one wave: its LDS writes land before its later reads)
+    Emit em{stage, shard_of((uint32_t)group, tile), 0u, 0u};   // (salted by the group, see tail_packed)
+    auto u64 = [](uint32_t lo, uint32_t hi) { return (uint64_t)lo | ((uint64_t)hi << 32); };
+    for (uint32_t r0 = 0; r0 < T; r0 += kWave) {
+        const uint32_t j = r0 + (uint32_t)lane;
+        const bool act = j < T;   // (an idle lane of the last round: the round's first slot, nothing loaded, stored or emitted)
+        const uint32_t slot = slots[act ? j : r0];
+        const uint32_t g = slot >> 6, l = slot & 63u;
+        const uint4* w = info + g * kDownInfoQuads;
+        const uint4 i0 = w[0], i1 = w[1], i4 = w[4], i5 = w[5], i6 = w[6];
+        const int32_t par = (int32_t)i0.x, e0 = (int32_t)i0.y, e1 = (int32_t)i0.z;
+        const uint64_t x = u64(i4.x, i4.y), s = u64(i4.z, i4.w), qx = u64(i5.x, i5.y), qs = u64(i5.z, i5.w);
+        const int64_t word = (int64_t)tile * kWave + l;
+        const uint32_t valid = act ? valid_mask(a, word) : 0u;
+        const bool cx = act && ((x >> l) & 1ull);
+        const bool dirty0 = act && ((u64(i6.x, i6.y) >> l) & 1ull), dirty1 = act && ((u64(i6.z, i6.w) >> l) & 1ull);
+        uint4* const p = a.sets + ((size_t)(a.dense_base + item0 + (int32_t)g) * a.tiles + tile) * REC;
+        // every load of the round issued before any is consumed ("initialise, then exec-masked
+        // load", see kid_fetch): the own code word (a simple lane's at its rank, else the
+        // consensus), an x lane's 16 planes, the parent's final, the children's dirty words
+        const uint4* csrc = ((s >> l) & 1ull) ? p + bits_below(s, l) : a.cons + word;
+        uint4 cw = make_uint4(0, 0, 0, 0), v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = make_uint4(0, 0, 0, 0);
+        if (act) cw = load_rec(csrc);
+        const uint32_t kx = bits_below(x, l);
+        if (cx) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = load_rec(p + kWave + q * kWave + kx);
+        }
+        const uint4* pb = a.sets + ((size_t)par * a.tiles + tile) * REC;
+        const uint4* fsrc = par == a.root_dense   ? a.root_final + word
+                            : ((qx >> l) & 1ull) ? pb + (uint32_t)__builtin_popcountll(qs) + bits_below(qx, l)
+                            : ((qs >> l) & 1ull) ? pb + bits_below(qs, l)
+                                                 : a.cons + word;
+        uint4 pf = make_uint4(0, 0, 0, 0);
+        if (act) pf = *fsrc;
+        uint4 L00 = make_uint4(0, 0, 0, 0), L01 = L00, L10 = L00, L11 = L00;
+        uint32_t m00 = 0, m01 = 0, m10 = 0, m11 = 0;
+        if (dirty0 && (int32_t)i1.x >= 0) {
+            L00 = a.leaf_planes[(size_t)i1.x * a.wpad + word];
+            m00 = ~0u;
+        }
+        if (dirty0 && (int32_t)i1.y >= 0) {
+            L01 = a.leaf_planes[(size_t)i1.y * a.wpad + word];
+            m01 = ~0u;
+        }
+        if (dirty1 && (int32_t)i1.z >= 0) {
+            L10 = a.leaf_planes[(size_t)i1.z * a.wpad + word];
+            m10 = ~0u;
+        }
+        if (dirty1 && (int32_t)i1.w >= 0) {
+            L11 = a.leaf_planes[(size_t)i1.w * a.wpad + word];
+            m11 = ~0u;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        uint32_t set[16], F[4], pres;
+        const uint32_t pc[4] = {pf.x, pf.y, pf.z, pf.w};
+        onehot_from_code(cw.x, cw.y, cw.z, cw.w, ~0u, set);
+        if (cx) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                set[4 * q + 0] = v[q].x;
+                set[4 * q + 1] = v[q].y;
+                set[4 * q + 2] = v[q].z;
+                set[4 * q + 3] = v[q].w;
+            }
+        }
+        resolve_final<Mode::kFitch>(a, false, word, set, nullptr, pc, F, pres);
+        if (cx) store_stream(p + (uint32_t)__builtin_popcountll(s) + kx, make_uint4(F[0], F[1], F[2], F[3]));   // final_slot
+        const uint32_t self_diff = pres & valid & ((F[0] ^ pc[0]) | (F[1] ^ pc[1]) | (F[2] ^ pc[2]) | (F[3] ^ pc[3]));
+        const uint32_t site0 = (uint32_t)(word * 32);
+        emit_stream(a, em, lane, i0.w, self_diff, site0, F[0], F[1], F[2], F[3], pc);
+        const uint4 i2 = w[2], i3 = w[3];   // (the children's ids: read where they are used, not held across the loads)
+        kid_emit_lanes(a, em, lane, e0, L00, L01, m00, m01, i2.x, i2.y, i2.z, valid, F, site0);
+        kid_emit_lanes(a, em, lane, e1, L10, L11, m10, m11, i3.x, i3.y, i3.z, valid, F, site0);
+    }
+    emit_flush<true>(a, em, lane);
+}
+
 // GROUP: items [split[g-1], split[g]) are the group's level g (split[-1] = 0, unused
 // splits = count), dense from dense_g[g].
-template <Mode M, bool AP, bool DENSE, bool SUB = false, bool GROUP = false>
+// G > 0: the packed form (down_packed) -- the level's a.count items in groups of G, one wave per
+// (group, tile).
+template <Mode M, bool AP, bool DENSE, bool SUB = false, bool GROUP = false, int G = 0>
 #ifndef PM_SK_GROUP_WAVES
 #define PM_SK_GROUP_WAVES 7
 #endif
@@ -1710,12 +1920,21 @@ template <Mode M, bool AP, bool DENSE, bool SUB = false, bool GROUP = false>
 #ifndef PM_SK_DOWN_WAVES
 #define PM_SK_DOWN_WAVES 6
 #endif
-__global__ __launch_bounds__(kBlock, GROUP ? (M == Mode::kSankoff ? PM_SK_GROUP_WAVES : SUB ? PM_SUB_DOWN_WAVES : 8) : SUB ? PM_SUB_DOWN_WAVES : (M == Mode::kFitch && AP) ? PM_DOWN_WAVES : (M == Mode::kSankoff && AP) ? PM_SK_DOWN_WAVES : 1) void k_down(DownArgs a) {
+__global__ __launch_bounds__(kBlock, G > 0 ? PM_DOWN_PACK_WAVES : GROUP ? (M == Mode::kSankoff ? PM_SK_GROUP_WAVES : SUB ? PM_SUB_DOWN_WAVES : 8) : SUB ? PM_SUB_DOWN_WAVES : (M == Mode::kFitch && AP) ? PM_DOWN_WAVES : (M == Mode::kSankoff && AP) ? PM_SK_DOWN_WAVES : 1) void k_down(DownArgs a) {
     __shared__ uint4 stage[kWavesPerBlock][kEntryQuads];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     int32_t item;
     int tile;
     wave_item(wave, a.tiles, item, tile);
+    if constexpr (G > 0) {
+        static_assert(M == Mode::kFitch && AP && DENSE && !SUB && !GROUP && G <= kWave && G * kWave <= 65536,
+                      "packed levels: Fitch, every leaf present, dense, slot = g * 64 + lane in 16 bits");
+        __shared__ uint4 info[kWavesPerBlock][G * kDownInfoQuads];
+        __shared__ uint16_t slots[kWavesPerBlock][G * kWave];
+        if (item >= (a.count + G - 1) / G) return;
+        down_packed<G>(a, item, tile, lane, stage[wave], info[wave], slots[wave]);
+        return;
+    }
     if (item >= a.count) return;   // whole wave leaves together
     const NodeDesc& d = a.desc[item];
     const int gen = !GROUP ? 0 : (item >= a.split[0]) + (item >= a.split[1]) + (item >= a.split[2]);
@@ -1786,10 +2005,6 @@ constexpr int kTailPack = PM_TAIL_PACK;
 #endif
 constexpr int64_t kTailPackMinWaves = PM_TAIL_PACK_MIN_WAVES;
 constexpr int kPackInfoQuads = 4;   // per item: {parent, enc, ix, iy}, id[0..3], {id[4], 0, 0, 0}, {px, ps}
-
-__device__ __forceinline__ uint32_t bits_below(uint64_t m, uint32_t l) {   // set bits of m below bit l (l per lane)
-    return (uint32_t)__builtin_popcountll(m & ((1ull << l) - 1ull));
-}
 
 template <Mode M, int G>
 __device__ __forceinline__ void tail_packed(const DownArgs& a, int32_t group, int tile, int lane, uint4* stage, uint4* info,

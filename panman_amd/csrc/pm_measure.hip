@@ -258,16 +258,43 @@ int pm_design_bytes(pm_ctx* c, double* out, int n) {
     auto in_cluster = [&](int32_t d) { return planned && ht.cl.slot_of[d] >= 0; };
     auto in_lds = [&](int32_t d) { return clu && in_cluster(d); };
     const bool down_lds = planned && ht.cl.down && (mode == PM_MODE_SANKOFF || !c->sub_down);
+    // Packed levels (PM_OPT_DOWN_PACK, Fitch): in_pack marks the nodes of the levels the last
+    // launch sequence packed -- or, the option off, would have packed.  Their live lanes
+    // (down_packed) are counted for out[20..30]; with the option on the own simple codes and the
+    // parent finals are read at live lanes only.
+    std::vector<uint8_t> in_pack(I, 0), under_root(I, 0);
+    if (mode == PM_MODE_FITCH)
+        for (size_t k = 0; k + 1 < c->down_pack_ranges.size(); k += 2)
+            for (int32_t i = 0; i < c->down_pack_ranges[k + 1]; ++i) in_pack[c->down_pack_ranges[k] + i] = 1;
+    for (int32_t k = ht.child_off[root]; k < ht.child_off[root + 1]; ++k)
+        if (ht.child_enc[k] >= 0) under_root[ht.child_enc[k]] = 1;
+    const bool packed_on = mode == PM_MODE_FITCH && c->down_pack;
+    double live_waves = 0.0, live_lanes = 0.0, live_hist[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // 0, 1-8, .., 57-64
     for (int32_t d = 0; d < I; ++d) {
         if (vnode[d]) continue;
         const int32_t e0 = ht.child_off[d], e1 = ht.child_off[d + 1];
         line[0] += 64.0;   // descriptor (a node's tiles run in adjacent waves)
         for (int t = 0; t < tiles; ++t) {
             const uint64_t* q = mk(d, t);
+            uint64_t live = ~0ull;   // the lanes reading own simple codes and parent finals
+            if (in_pack[d]) {
+                auto s_kid = [&](int32_t e) { return sub && ht.child_enc[e] >= 0 && vnode[ht.child_enc[e]] > 2; };
+                live = q[0] | q[3];
+                for (int32_t k = e0; k < e1 && k < e0 + 2; ++k) {   // the descriptor's first two (S2 / S3 children dropped)
+                    const int32_t ch = ht.child_enc[k];
+                    if (ch < 0) live |= q[0];
+                    else if (vnode[ch] && vnode[ch] <= 2) live |= q[6 + (k - e0) - (k > e0 && s_kid(e0))];
+                }
+                if (under_root[d]) live = ~0ull;
+                live_waves += 1.0;
+                live_lanes += popc(live);
+                live_hist[(popc(live) + 7) / 8] += 1.0;
+                if (!packed_on) live = ~0ull;
+            }
             // level kernels: mask record (half a line), own record (simple codes by rank, then
             // the complex areas), parent finals (every non-consensus lane)
-            line[0] += 64.0 + LB * (ceil8(popc(q[1])) + cx_areas * ceil8(popc(q[0])));
-            if (d != root && !(down_lds && in_cluster(d))) line[1] += LB * rank_lines(q[3] | q[4], q[4], q[3]);
+            line[0] += 64.0 + LB * (rank_lines(live, q[1], 0) + cx_areas * ceil8(popc(q[0])));
+            if (d != root && !(down_lds && in_cluster(d))) line[1] += LB * rank_lines((q[3] | q[4]) & live, q[4], q[3]);
             const uint64_t dirty_m = d == root ? ~0ull : q[2];
             const uint64_t dleaf_m = leaf_rule && d != root ? q[0] : dirty_m;
             const double rec = 64.0 + lane * popc(q[1]) + cx_full * popc(q[0]);
@@ -331,12 +358,14 @@ int pm_design_bytes(pm_ctx* c, double* out, int n) {
                 }
             }
             // pre-order: own record, parent final (non-consensus lanes), compact final out
-            down += rec;
-            part[3] += rec;
+            // (packed levels: simple codes and parent finals at live lanes only)
+            const double rec_down = rec - lane * popc(q[1] & ~live);
+            down += rec_down;
+            part[3] += rec_down;
             if (d == root) {
                 down += 2.0 * word_row;   // forced / root final
             } else {
-                const double pf = down_lds && in_cluster(d) ? 0.0 : lane * popc(q[3] | q[4]);
+                const double pf = down_lds && in_cluster(d) ? 0.0 : lane * popc((q[3] | q[4]) & live);
                 down += pf + lane * popc(q[0]);
                 part[4] += pf;
                 part[6] += lane * popc(q[0]);
@@ -351,6 +380,10 @@ int pm_design_bytes(pm_ctx* c, double* out, int n) {
     out[4] = (double)records;
     for (int k = 0; k < 9 && 5 + k < n; ++k) out[5 + k] = part[k];
     for (int k = 0; k < 6 && 14 + k < n; ++k) out[14 + k] = line[k];
+    // live lanes per (node, tile) wave of the packed (or packable) levels: waves, lanes, histogram
+    if (20 < n) out[20] = live_waves;
+    if (21 < n) out[21] = live_lanes;
+    for (int k = 0; k < 9 && 22 + k < n; ++k) out[22 + k] = live_hist[k];
     return PM_OK;
 }
 
