@@ -161,6 +161,9 @@ int pm_set_stream(pm_ctx* ctx, void* hip_stream);
  *   PM_OPT_GFA_BATCH_BYTES (default 1 GiB, at least 4096): pm_gfa / pm_gfa_fd produce and
  *                  stream the "P" lines in batches of whole lines of at most this many bytes
  *                  (always at least one line).  The text does not depend on it.
+ *   PM_OPT_GFA_IN_BATCH_SITES (default and most 2^24 - 1, the most sites pm_leaves_upload takes;
+ *                  at least 1): pm_gfa_build uploads and runs the block columns in batches of at
+ *                  most this many.  The result does not depend on it.
  * (Option ids 1, 4, 5 and 11 -- subtree-region, heavy-path-chain and level-band schedules,
  * tail records overlapped with the pre-order levels -- were measured slower than, or no
  * faster than, the level kernels on MI355X and removed.) */
@@ -181,6 +184,7 @@ int pm_set_stream(pm_ctx* ctx, void* hip_stream);
 #define PM_OPT_MAF_BATCH_BYTES 20
 #define PM_OPT_GFA_BATCH_BYTES 21
 #define PM_OPT_DOWN_PACK 22
+#define PM_OPT_GFA_IN_BATCH_SITES 23
 int pm_set_option(pm_ctx* ctx, int option, int64_t value);
 /* Accumulate per-kernel-class device time with HIP events (see pm_kernel_times). */
 int pm_set_profiling(pm_ctx* ctx, int enable);
@@ -199,6 +203,21 @@ int pm_tree_upload(pm_ctx* ctx, const pm_tree* tree);
  *     PanGraph driver does for leaves lacking a block (src/panman.cpp:1026-1028). */
 int pm_leaves_upload(pm_ctx* ctx, int64_t num_sites, const uint8_t* codes4, int64_t row_stride,
                      const int32_t* node_row, const uint8_t* present, int64_t present_stride);
+
+/* The same upload from sparse rows: equivalent to pm_leaves_upload (present = NULL) of the dense
+ * matrix that holds `fill_code` everywhere except code[i] at (row, site[i]) for the entries
+ * i in [row_off[row], row_off[row + 1]) of each row.  For matrices that are almost entirely one
+ * code, as the block states of a GFA are (paths x segments, src/panman.cpp:784-797: "absent"
+ * wherever the path has no step): the host validates and uploads only the three arrays, and a
+ * kernel expands them into the packed staging rows on the device.
+ *   row_off [num_rows + 1], row_off[0] = 0, non-decreasing;
+ *   site    [nnz] strictly increasing within a row, 0 <= site < num_sites;
+ *   code    [nnz] 0..15; fill_code 0..15;
+ *   node_row[node] < num_rows (-1: the leaf is absent).
+ * The same state and errors as pm_leaves_upload; PM_ERR_ARG for an entry or a node_row outside
+ * those ranges. */
+int pm_leaves_upload_sparse(pm_ctx* ctx, int64_t num_sites, int32_t num_rows, const int64_t* row_off,
+                            const int32_t* site, const uint8_t* code, uint8_t fill_code, const int32_t* node_row);
 
 /* Per-site constants (packed codes, ceil(S/2) bytes each).
  *   consensus: the root's parent state, i.e. the block consensus character
@@ -562,6 +581,35 @@ int pm_reroot(pm_ctx* ctx, const pm_panmat* tree, const char* leaf, pm_panman** 
  * Without a reference the main-column root forcing follows oneTBB's iteration order of
  * the per-block sequences.  Result: a one-tree pm_panman. */
 int pm_pangraph_build(pm_ctx* ctx, const char* json, const char* newick, const char* reference, pm_panman** out);
+
+/* Drop-in for Tree(gfa, newick, FILE_TYPE::GFA) (src/panman.cpp:728-819; CLI -G/-N,
+ * src/panmanUtils.cpp:1326-1362) followed by TreeGroup({T}): `gfa_text` and `newick` are file
+ * contents (the Newick is the first line of its text).  Result: a one-tree pm_panman.
+ *   parse    line by line, fields split on tab as stringSplit does (src/panman.cpp:265-300).
+ *            "S": nodes[f[1]] = f[2]; "P": the steps of f[2] split on ',', a step's name all but
+ *            its last character, forward when that is '+'; a later duplicate of either wins; every
+ *            other record type and blank lines are ignored.  Paths are taken in byte order of
+ *            their names (std::map).
+ *   blocks   GfaGraph::GfaGraph (:6060-6142): the first path seeds the consensus order, each later
+ *            path is chain_align'ed against it (src/chaining.cpp), its unmatched steps become new
+ *            blocks -- a repeated or moved segment is a second block with the same sequence.
+ *            Block i has primary id i and Block(i, sequence) of its segment (:777-779); there are
+ *            no gaps, no block gaps and no nucleotide mutations.
+ *   states   per path the two-pointer walk against blocks 0..T-1 (:6144-6193): absent where the
+ *            path lacks the block, else forward / reverse by the step's strand (:784-797).
+ *   Fitch    PM_MODE_BLOCK_FITCH over every block (:798-800), also on a tree with polytomies
+ *            (where the PanGraph driver switches to Sankoff); the root's parent state is absent
+ *            and nothing is forced.  A tree leaf no path names is absent from every column; a
+ *            path no leaf names takes part in the block order only.  The states reach the device
+ *            as sparse rows (pm_leaves_upload_sparse: the steps, fill = absent) in batches of
+ *            PM_OPT_GFA_IN_BATCH_SITES columns.
+ *   Within a node the block mutations are in ascending block id (the reference's order is
+ *   TBB-scheduled), (type, inversion) as src/fitchSankoff.cpp:279-303.
+ * Errors (PM_ERR_ARG, the message names the offender): a step naming an undefined segment (the
+ * reference makes an empty block), an empty step, an "S" or "P" line of fewer than 3 fields, no
+ * "P" line, a Newick that does not parse.  Phase log: gfain.parse, gfain.chain, gfain.upload,
+ * gfain.run, gfain.assemble.  Replaces the ctx's tree and columns. */
+int pm_gfa_build(pm_ctx* ctx, const char* gfa_text, const char* newick, pm_panman** out);
 
 /* ---- summary ------------------------------------------------------------------------- */
 /* Drop-in for Tree::printSummary (src/summary.cpp:257-273; CLI --summary, src/panmanUtils.cpp:

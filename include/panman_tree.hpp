@@ -85,7 +85,7 @@ class Tree {
     // Tree(std::ifstream& fin, std::ifstream& secondFin, FILE_TYPE ftype, std::string reference)
     // (src/panman.hpp:825-826): MSA / MSA_OPTIMIZE -- fin = aligned FASTA, secondFin = Newick
     // (src/panman.cpp:1274-1649); PANGRAPH -- fin = PanGraph JSON, secondFin = Newick
-    // (:820-1273).  GFA input is not on the GPU path.
+    // (:820-1273); GFA -- fin = GFA text, secondFin = Newick (:728-819; `reference` unused).
     Tree(std::istream& fin, std::istream& secondFin, FILE_TYPE ftype, const std::string& reference = "",
          int device = 0)
         : device_(device) {
@@ -103,6 +103,11 @@ class Tree {
             pm_panman* out = nullptr;
             ctx.check(pm_pangraph_build(ctx.c, first.c_str(), newick.c_str(), reference.c_str(), &out),
                       "pm_pangraph_build");
+            file_ = detail::own(out);
+        } else if (ftype == GFA) {
+            detail::Ctx ctx(device);
+            pm_panman* out = nullptr;
+            ctx.check(pm_gfa_build(ctx.c, first.c_str(), newick.c_str(), &out), "pm_gfa_build");
             file_ = detail::own(out);
         } else {
             throw Error("this FILE_TYPE is not on the GPU path");

@@ -51,6 +51,8 @@ _SIGS = {
     "pm_tree_upload": (C.c_int, [C.c_void_p, C.POINTER(Tree)]),
     "pm_leaves_upload": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                    C.c_void_p, C.c_int64]),
+    "pm_leaves_upload_sparse": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_uint8, C.c_void_p]),
     "pm_sites_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pm_run": (C.c_int, [C.c_void_p, C.c_int]),
     "pm_mutation_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
@@ -99,6 +101,7 @@ _SIGS = {
     "pm_panman_write": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_int]),
     "pm_reroot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]),
     "pm_pangraph_build": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]),
+    "pm_gfa_build": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]),
     "pm_comm_unique_id": (C.c_int, [C.c_void_p, C.c_int64]),
     "pm_comm_init_rank": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "pm_comm_init_all": (C.c_int, [C.c_void_p, C.c_int]),

@@ -1,5 +1,5 @@
 // panmanUtils-compatible command line for the GPU path (src/panmanUtils.cpp:128-182 option
-// table, :1302-1325 PanMAN load, :1409-1465 MSA build, :271-299 writePanMAN, :385-415 and
+// table, :1302-1325 PanMAN load, :1409-1465 MSA build, :1326-1362 GFA build, :271-299 writePanMAN, :385-415 and
 // :458-490 FASTA / aligned FASTA, :699-732 GFA, :741-763 MAF, :766-786 Newick).  Only the commands on the accelerated
 // path are implemented; any other reference command is rejected with a message.
 #include <fcntl.h>
@@ -46,6 +46,7 @@ const Spec kSpecs[] = {
     {"input-panman", 'I', true, "Input PanMAN file path"},
     {"input-msa", 'M', true, "Input MSA file (FASTA format) to build a PanMAN"},
     {"input-pangraph", 'P', true, "Input PanGraph JSON file to build a PanMAN"},
+    {"input-gfa", 'G', true, "Input GFA file to build a PanMAN"},
     {"input-newick", 'N', true, "Input tree topology as Newick string"},
     {"summary", 's', false, "Print PanMAN summary"},
     {"newick", 't', false, "Print newick string of all trees in a PanMAN"},
@@ -66,7 +67,7 @@ const Spec kSpecs[] = {
 };
 
 // Reference commands outside the accelerated path: recognised so the error is explicit.
-const char* const kOther[] = {"input-gfa", "impute", "create-network", "printTips",
+const char* const kOther[] = {"impute", "create-network", "printTips",
                               "subnet", "vcf", "annotate",
                               "aa-translation", "extended-newick", "printMutations", "acr", "index",
                               "toUsher"};
@@ -362,6 +363,58 @@ int build_from_pangraph(const Options& o, int device) {
     return 0;
 }
 
+// -G graph.gfa -N tree.nwk -o out (src/panmanUtils.cpp:1326-1362)
+int build_from_gfa(const Options& o, int device) {
+    if (!o.has("input-newick")) {
+        print_error("File containing newick string not provided!");
+        return 1;
+    }
+    if (!o.has("output-file")) {
+        print_error("Output file not provided!");
+        usage(std::cout);
+        return 1;
+    }
+    std::string text, newick;
+    if (!read_file(o.get("input-gfa"), text)) {
+        print_error("cannot read " + o.get("input-gfa"));
+        return 1;
+    }
+    if (!read_file(o.get("input-newick"), newick)) {
+        print_error("cannot read " + o.get("input-newick"));
+        return 1;
+    }
+    std::cout << "Creating PanMAN from GFA and Newick" << std::endl;
+    pm_ctx* ctx = nullptr;
+    if (pm_create(device, &ctx) != PM_OK) {
+        print_error("no HIP device");
+        return 1;
+    }
+    const auto t0 = Clock::now();
+    pm_panman* res = nullptr;
+    if (pm_gfa_build(ctx, text.c_str(), newick.c_str(), &res) != PM_OK) {
+        print_error(pm_last_error(ctx));
+        pm_destroy(ctx);
+        return 1;
+    }
+    std::cout << "Data load time: " << ns_since(t0) << " nanoseconds \n";
+    std::cout << "Writing PanMAN" << std::endl;
+    ::mkdir("./panman", 0777);
+    const std::string out = "./panman/" + o.get("output-file") + ".panman";
+    pm_panmat view;
+    pm_panman_tree(res, 0, &view);
+    const pm_panmat* list[1] = {&view};
+    const auto w0 = Clock::now();
+    const int rc = pm_panman_write(out.c_str(), list, 1, 1);
+    std::cout << "\nNetwork Write execution time: " << ns_since(w0) << " nanoseconds\n";
+    pm_panman_free(res);
+    pm_destroy(ctx);
+    if (rc != PM_OK) {
+        print_error("cannot write " + out);
+        return 1;
+    }
+    return 0;
+}
+
 // --protobuf2capnp -I old.panman -o out (src/panmanUtils.cpp:939-952, 1267-1268): the older
 // Protobuf PanMAN read and written back as ./panman/<out>.panman (writePanMAN, :271-299).
 int protobuf2capnp(const Options& o) {
@@ -606,12 +659,13 @@ int run(int argc, char** argv) {
         }
     } warm;
     if (const char* nw = std::getenv("PM_CLI_NO_WARMUP");
-        !(nw && nw[0] == '1') && o.has("input-panman") && !o.has("input-msa") && !o.has("input-pangraph"))
+        !(nw && nw[0] == '1') && o.has("input-panman") && !o.has("input-msa") && !o.has("input-pangraph") && !o.has("input-gfa"))
         warm.t = std::thread([device] { (void)pm_warmup(device); });
+    if (o.has("input-gfa")) return build_from_gfa(o, device);
     if (o.has("input-pangraph")) return build_from_pangraph(o, device);
     if (o.has("input-msa")) return build_from_msa(o, devices);
     if (o.has("input-panman")) return from_panman(o, devices);
-    print_error("no input: give -I <file.panman> or -M <msa> -N <newick>");
+    print_error("no input: give -I <file.panman>, or -M <msa>, -P <pangraph.json> or -G <graph.gfa> with -N <newick>");
     usage(std::cerr);
     return 1;
 }

@@ -548,6 +548,11 @@ int pm_set_option(pm_ctx* c, int option, int64_t value) {
         c->gfa_batch_bytes = value;
         return PM_OK;
     }
+    if (option == PM_OPT_GFA_IN_BATCH_SITES) {
+        if (value < 1 || value > kMaxUploadSites) return fail(c, PM_ERR_ARG, "PM_OPT_GFA_IN_BATCH_SITES: 1 .. 2^24 - 1 sites");
+        c->gfa_in_batch_sites = value;
+        return PM_OK;
+    }
     if (option == PM_OPT_GROUP_WAVES) {
         if (value < 0) return fail(c, PM_ERR_ARG, "PM_OPT_GROUP_WAVES: >= 0 waves");
         c->group_waves = value;
@@ -1376,6 +1381,62 @@ int pm_leaves_upload(pm_ctx* c, int64_t S, const uint8_t* codes4, int64_t row_st
     c->has_leaves = true;
     c->sub_planes_ok = false;
     return build_sub_planes(c);
+}
+
+int pm_leaves_upload_sparse(pm_ctx* c, int64_t S, int32_t num_rows, const int64_t* row_off, const int32_t* site,
+                            const uint8_t* code, uint8_t fill_code, const int32_t* node_row) {
+    if (!c) return PM_ERR_ARG;
+    if (!c->has_tree) return fail(c, PM_ERR_STATE, "upload the tree first");
+    if (S <= 0 || S >= (int64_t)1 << 24 || num_rows < 0 || !row_off || !node_row || fill_code > 15)
+        return fail(c, PM_ERR_ARG, "bad leaf matrix arguments (0 < sites < 2^24)");
+    if (row_off[0] != 0) return fail(c, PM_ERR_ARG, "sparse leaf rows: row_off[0] must be 0");
+    const int64_t nnz = row_off[num_rows];
+    if (nnz > 0 && (!site || !code)) return fail(c, PM_ERR_ARG, "bad leaf matrix arguments (0 < sites < 2^24)");
+    for (int32_t r = 0; r < num_rows; ++r) {
+        if (row_off[r + 1] < row_off[r]) return fail(c, PM_ERR_ARG, "sparse leaf rows: row_off decreases at row " + std::to_string(r));
+        for (int64_t i = row_off[r]; i < row_off[r + 1]; ++i) {
+            if (site[i] < 0 || site[i] >= S)
+                return fail(c, PM_ERR_ARG, "sparse leaf rows: site out of range in row " + std::to_string(r));
+            if (i > row_off[r] && site[i] <= site[i - 1])
+                return fail(c, PM_ERR_ARG, "sparse leaf rows: sites not strictly increasing in row " + std::to_string(r));
+            if (code[i] > 15) return fail(c, PM_ERR_ARG, "sparse leaf rows: code above 15 in row " + std::to_string(r));
+        }
+    }
+    for (int32_t l = 0; l < c->dt.num_leaves; ++l)
+        if (node_row[c->ht.leaf_id[l]] >= num_rows)
+            return fail(c, PM_ERR_ARG, "sparse leaf rows: node_row names row " + std::to_string(node_row[c->ht.leaf_id[l]]) +
+                                           " of " + std::to_string(num_rows));
+    (void)hipSetDevice(c->device);
+    // staging rows of whole 32-bit words, expanded on the device from the three arrays
+    const int64_t stride_words = ((S + 1) / 2 + 3) / 4;
+    int64_t* d_off = nullptr;
+    int32_t* d_site = nullptr;
+    uint8_t* d_code = nullptr;
+    uint32_t* d_rows4 = nullptr;
+    hipError_t e;
+    if ((e = dev_alloc(&d_off, (size_t)num_rows + 1)) != hipSuccess || (e = dev_alloc(&d_site, (size_t)nnz)) != hipSuccess ||
+        (e = dev_alloc(&d_code, (size_t)nnz)) != hipSuccess ||
+        (e = dev_alloc(&d_rows4, (size_t)num_rows * stride_words)) != hipSuccess) {
+        dev_free(d_off);
+        dev_free(d_site);
+        dev_free(d_code);
+        dev_free(d_rows4);
+        return fail(c, PM_ERR_OOM, "leaf staging");
+    }
+    e = hipMemcpyAsync(d_off, row_off, sizeof(int64_t) * ((size_t)num_rows + 1), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && nnz) e = hipMemcpyAsync(d_site, site, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && nnz) e = hipMemcpyAsync(d_code, code, (size_t)nnz, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = launch_expand_sparse(c, d_off, d_site, d_code, fill_code, num_rows, stride_words, d_rows4);
+    int rc = PM_OK;
+    if (e != hipSuccess) rc = hip_fail(c, e, "leaf upload");
+    // (leaves_install synchronises the stream before it returns: the host arrays are free then)
+    else rc = leaves_install(c, S, reinterpret_cast<const uint8_t*>(d_rows4), stride_words * 4, node_row);
+    if (e != hipSuccess) (void)hipStreamSynchronize(c->stream);
+    dev_free(d_off);
+    dev_free(d_site);
+    dev_free(d_code);
+    dev_free(d_rows4);
+    return rc;
 }
 
 int pm_sites_upload(pm_ctx* c, const uint8_t* consensus4, const uint8_t* forced4) {

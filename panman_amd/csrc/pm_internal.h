@@ -48,6 +48,8 @@ constexpr int kFitchRecQuads = kCxCompact ? 6 : 5;
 constexpr int kMaskWords = 8;     // record masks per (node, tile): complex, simple, dirty, parent's
                                   // complex, parent's simple, an S2 / S3 node's pushed dirty lanes,
                                   // Fitch: the first / second child's dirty lanes (one 64-B line)
+// The most sites one leaf upload takes (a record's site field is 24 bits; pm_leaves_upload).
+constexpr int64_t kMaxUploadSites = ((int64_t)1 << 24) - 1;
 // Grouped post-order launches (PM_OPT_UP_GROUP): heights of at most this many nodes group.
 #ifndef PM_UP_GROUP_NODES
 #define PM_UP_GROUP_NODES 2048
@@ -392,6 +394,7 @@ struct pm_ctx {
     int64_t vcf_batch_bytes = (int64_t)1 << 30;   // pm_vcf: genotype text per device batch (PM_OPT_VCF_BATCH_BYTES)
     int64_t maf_batch_bytes = (int64_t)1 << 30;   // pm_maf: text per device batch of whole lines (PM_OPT_MAF_BATCH_BYTES)
     int64_t gfa_batch_bytes = (int64_t)1 << 30;   // pm_gfa: text per device batch of whole P lines (PM_OPT_GFA_BATCH_BYTES)
+    int64_t gfa_in_batch_sites = pm::kMaxUploadSites; // pm_gfa_build: block columns per upload and run (PM_OPT_GFA_IN_BATCH_SITES)
 };
 
 namespace pm {
@@ -431,6 +434,8 @@ static_assert(sizeof(pm_mut) == 8, "pm_mut is {node, site_info}");
 hipError_t launch_score(pm_ctx* c);
 hipError_t launch_pack_codes(pm_ctx* c, const uint8_t* d_codes4, int64_t row_stride, const int32_t* d_row_of_leaf,
                              const uint8_t* d_present, int64_t present_stride);
+hipError_t launch_expand_sparse(pm_ctx* c, const int64_t* d_row_off, const int32_t* d_site, const uint8_t* d_code,
+                                uint8_t fill_code, int32_t rows, int64_t stride_words, uint32_t* d_out);
 hipError_t launch_pack_sites(pm_ctx* c, const uint8_t* d_codes4, uint4* dst);
 hipError_t launch_synth(pm_ctx* c, int64_t site_begin, uint64_t seed);
 hipError_t launch_unpack_leaf_codes(pm_ctx* c, int64_t s0, int64_t ns, uint8_t* d_out);

@@ -23,6 +23,7 @@
 #include <utility>
 #include <vector>
 
+#include "pm_chain.h"
 #include "pm_internal.h"
 #include "pm_json.h"
 #include "pm_newick.h"
@@ -31,153 +32,9 @@
 namespace pm {
 namespace {
 
-uint8_t code_of(char ch) {
-    switch (ch) {
-        case 'A': return 1;  case 'C': return 2;  case 'G': return 4;  case 'T': return 8;
-        case 'R': return 5;  case 'Y': return 10; case 'S': return 6;  case 'W': return 9;
-        case 'K': return 12; case 'M': return 3;  case 'B': return 14; case 'D': return 13;
-        case 'H': return 11; case 'V': return 7;  case 'N': return 15;
-        default: return 0;
-    }
-}
-
 std::string upper(std::string s) {
     for (char& c : s) c = (char)std::toupper((unsigned char)c);
     return s;
-}
-
-// ---- src/chaining.cpp -----------------------------------------------------------------
-using Pt = std::pair<int, int>;
-const Pt kOrigin(-1, -1);
-
-struct HashPair {   // src/chaining.cpp:24-37
-    size_t operator()(const Pt& p) const {
-        const size_t h1 = std::hash<int>{}(p.first), h2 = std::hash<int>{}(p.second);
-        return h1 != h2 ? h1 ^ h2 : h1;
-    }
-};
-
-struct RangeNode {
-    Pt point;
-    int left = -1, right = -1;
-};
-
-int build_range_tree(std::vector<Pt>& pts, int start, int end, std::vector<RangeNode>& nodes) {   // :69-82
-    if (start > end) return -1;
-    std::sort(pts.begin() + start, pts.begin() + end + 1, [](const Pt& a, const Pt& b) { return a.first < b.first; });
-    const int mid = (start + end) / 2;
-    const int me = (int)nodes.size();
-    nodes.push_back(RangeNode{pts[mid]});
-    const int l = build_range_tree(pts, start, mid - 1, nodes);
-    const int r = build_range_tree(pts, mid + 1, end, nodes);
-    nodes[me].left = l;
-    nodes[me].right = r;
-    return me;
-}
-
-void query_range(const std::vector<RangeNode>& nodes, int root, Pt lo, Pt hi, std::vector<Pt>& out) {   // :87-100
-    if (root < 0) return;
-    const RangeNode& n = nodes[root];
-    if (n.point.first >= lo.first && n.point.first <= hi.first && n.point.second >= lo.second &&
-        n.point.second <= hi.second)
-        out.push_back(n.point);
-    if (n.left >= 0 && lo.first <= n.point.first) query_range(nodes, n.left, lo, hi, out);
-    if (n.right >= 0 && hi.first >= n.point.first) query_range(nodes, n.right, lo, hi, out);
-}
-
-using ScoreMap = std::unordered_map<Pt, std::pair<int, Pt>, HashPair>;
-
-void find_chain(const std::vector<RangeNode>& nodes, int root, Pt point, ScoreMap& map, int K) {   // :102-143
-    const int match = 50;
-    if (point.first == 0 && point.second == 0) {
-        map[point] = {match, Pt(-1, -1)};
-        return;
-    }
-    std::vector<Pt> result;
-    query_range(nodes, root, Pt(point.first - K > 0 ? point.first - K : 0, point.second - K > 0 ? point.second - K : 0),
-                Pt(point.first - 1, point.second - 1), result);
-    int best = 10;
-    Pt best_node = kOrigin;
-    int xb = -1, yb = -1;
-    for (auto it = result.rbegin(); it != result.rend(); ++it) {
-        const Pt p = *it;
-        if (p.first <= xb && p.second <= yb) continue;
-        const int cost = -(point.first - p.first + point.second - p.second);
-        if (cost + map[p].first + match > best) {
-            best = cost + map[p].first + match;
-            best_node = p;
-        }
-        if (xb < p.first) xb = p.first - 1;
-        if (yb < p.second) yb = p.second - 1;
-    }
-    map[point] = {best, best_node};
-}
-
-std::vector<Pt> chaining(const std::vector<std::string>& cons, const std::vector<std::string>& sample) {   // :146-230
-    std::vector<Pt> chain;
-    const int K = 4000;
-    std::vector<Pt> pts;
-    for (size_t i = 0; i < cons.size(); ++i)
-        for (size_t j = 0; j < sample.size(); ++j)
-            if (cons[i] == sample[j]) pts.emplace_back((int)i, (int)j);
-    std::sort(pts.begin(), pts.end());   // comparePoint: (x, y), points are distinct
-    std::vector<RangeNode> nodes;
-    nodes.reserve(pts.size());
-    const int root = build_range_tree(pts, 0, (int)pts.size() - 1, nodes);
-    if (pts.empty()) return chain;
-    ScoreMap map;
-    for (const Pt& p : pts) map[p] = {-1, kOrigin};
-    for (const Pt& p : pts) find_chain(nodes, root, p, map, K);
-    int best = -1;
-    Pt seed{};
-    for (const auto& m : map)
-        if (m.second.first > best) {
-            best = m.second.first;
-            seed = m.first;
-        }
-    while (true) {
-        chain.push_back(seed);
-        seed = map[seed].second;
-        if (seed == kOrigin) break;
-    }
-    return chain;
-}
-
-void build_consensus(const std::vector<Pt>& chain, const std::vector<std::string>& cons,
-                     const std::vector<std::string>& sample, const std::vector<size_t>& int_cons,
-                     std::vector<size_t>& int_sample, size_t& num_blocks, std::vector<std::string>& cons_new,
-                     std::vector<size_t>& int_cons_new, std::unordered_map<int, std::string>& int_to_string) {   // :233-277
-    int pc = -1, ps = -1;
-    for (auto it = chain.rbegin(); it != chain.rend(); ++it) {
-        const int cc = it->first, sc = it->second;
-        for (int j = pc + 1; j < cc; ++j) {
-            cons_new.push_back(cons[j]);
-            int_cons_new.push_back(int_cons[j]);
-        }
-        for (int j = ps + 1; j < sc; ++j) {
-            cons_new.push_back(sample[j]);
-            int_sample.push_back(num_blocks);
-            int_to_string[(int)num_blocks] = sample[j];
-            int_cons_new.push_back(num_blocks);
-            ++num_blocks;
-        }
-        cons_new.push_back(cons[cc]);
-        int_sample.push_back(int_cons[cc]);
-        int_cons_new.push_back(int_cons[cc]);
-        pc = cc;
-        ps = sc;
-    }
-    for (int j = pc + 1; j < (int)cons.size(); ++j) {
-        cons_new.push_back(cons[j]);
-        int_cons_new.push_back(int_cons[j]);
-    }
-    for (int j = ps + 1; j < (int)sample.size(); ++j) {
-        cons_new.push_back(sample[j]);
-        int_sample.push_back(num_blocks);
-        int_to_string[(int)num_blocks] = sample[j];
-        int_cons_new.push_back(num_blocks);
-        ++num_blocks;
-    }
 }
 
 // ---- src/rotation.cpp (ALLOW_INVERSIONS undefined: never inverted) -------------------
@@ -449,16 +306,6 @@ void group(std::vector<Tup>& v, bool gap, PanmanTree& out) {
         }
     }
     if (!v.empty()) emit(start, v.size());
-}
-
-std::vector<uint32_t> encode_block(const std::string& seq) {   // Block(i, seq), src/panman.cpp:246-257
-    std::vector<uint32_t> w;
-    for (size_t i = 0; i < seq.size(); i += 8) {
-        uint32_t x = 0;
-        for (size_t j = i; j < std::min(i + 8, seq.size()); ++j) x ^= (uint32_t)code_of(seq[j]) << (4 * (7 - (j - i)));
-        w.push_back(x);
-    }
-    return w;
 }
 
 int build(pm_ctx* c, const char* json_text, const char* newick_c, const char* ref_c, PanmanTree& out) {

@@ -198,6 +198,43 @@ hipError_t launch_pack_codes(pm_ctx* c, const uint8_t* d_codes4, int64_t row_str
     return hipGetLastError();
 }
 
+// Sparse leaf rows -> the packed 4-bit staging rows k_pack_leaves reads (pm_leaves_upload_sparse).
+// Thread = one 32-bit word of one row (sites 8w .. 8w + 7, low nibble = even site): the row's
+// first entry at or after site 8w by binary search, then its at most 8 entries of the word merged
+// over the fill pattern.  Every word is written once, coalesced; no clear pass, no atomics.
+__global__ __launch_bounds__(256) void k_expand_sparse(const int64_t* __restrict__ row_off, const int32_t* __restrict__ site,
+                                                       const uint8_t* __restrict__ code, uint32_t fill8, int32_t rows,
+                                                       int64_t stride_words, uint32_t* __restrict__ out) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (int64_t)rows * stride_words) return;
+    const int32_t row = (int32_t)(t / stride_words);
+    const int64_t s0 = (t - (int64_t)row * stride_words) * 8;
+    const int64_t end = row_off[row + 1];
+    int64_t lo = row_off[row], hi = end;
+    while (lo < hi) {   // first entry with site >= s0
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (site[mid] < s0) lo = mid + 1;
+        else hi = mid;
+    }
+    uint32_t w = fill8;
+    for (int k = 0; k < 8 && lo < end; ++k, ++lo) {
+        const int64_t d = (int64_t)site[lo] - s0;
+        if (d >= 8) break;
+        const int sh = 4 * (int)d;
+        w = (w & ~(15u << sh)) | ((uint32_t)(code[lo] & 15u) << sh);
+    }
+    out[t] = w;
+}
+
+hipError_t launch_expand_sparse(pm_ctx* c, const int64_t* d_row_off, const int32_t* d_site, const uint8_t* d_code,
+                                uint8_t fill_code, int32_t rows, int64_t stride_words, uint32_t* d_out) {
+    const int64_t n = (int64_t)rows * stride_words;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_expand_sparse, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, d_row_off, d_site, d_code,
+                       (uint32_t)(fill_code & 15u) * 0x11111111u, rows, stride_words, d_out);
+    return hipGetLastError();
+}
+
 hipError_t launch_pack_sites(pm_ctx* c, const uint8_t* d_codes4, uint4* dst) {
     const int64_t wpad = (int64_t)((c->words + kWave - 1) / kWave) * kWave;
     hipLaunchKernelGGL(k_pack_sites, dim3(blocks_for(wpad, 256)), dim3(256), 0, c->stream, d_codes4, dst,
