@@ -97,6 +97,16 @@ __device__ __forceinline__ uint32_t code_at(uint32_t b0, uint32_t b1, uint32_t b
            (((b3 >> bit) & 1u) << 3);
 }
 
+// decimal digits of v (the text kernels of pm_vcf / pm_maf / pm_gfa)
+__device__ __forceinline__ int digits_of(uint32_t v) {
+    int d = 1;
+    while (v >= 10) {
+        v /= 10;
+        ++d;
+    }
+    return d;
+}
+
 // 64-lane inclusive prefix sum by DPP lane moves (no LDS round trips): shifts of 1, 2, 4, 8
 // inside each 16-lane row, then row 0's / rows 0-1's totals broadcast to the rows above
 // (row_bcast:15, row_bcast:31 -- the gfx9 family's DPP broadcasts).

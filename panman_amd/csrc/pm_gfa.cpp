@@ -14,55 +14,18 @@
 // the reference's other branch (gfa.cpp:13-118): whole blocks as segments, presence from a host
 // walk, the "P" lines through the same kernels.
 #include <algorithm>
-#include <cerrno>
 #include <cstdlib>
-#include <cstring>
 #include <map>
-#include <new>
 #include <set>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
+#include "pm_dev.h"
 #include "pm_replay.h"
 
 namespace pm {
 namespace {
-
-template <class T>
-struct Dev {   // a device array released on scope exit
-    T* p = nullptr;
-    Dev() = default;
-    Dev(const Dev&) = delete;
-    Dev& operator=(const Dev&) = delete;
-    ~Dev() { reset(); }
-    void reset() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    hipError_t alloc(size_t n, bool zero, hipStream_t s) {
-        reset();
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), sizeof(T) * std::max<size_t>(n, 1));
-        if (e != hipSuccess) p = nullptr;
-        else if (zero) e = hipMemsetAsync(p, 0, sizeof(T) * std::max<size_t>(n, 1), s);
-        return e;
-    }
-    hipError_t put(const std::vector<T>& v, hipStream_t s) {
-        hipError_t e = alloc(v.size(), false, s);
-        if (e == hipSuccess && !v.empty()) e = hipMemcpyAsync(p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, s);
-        return e;
-    }
-    hipError_t get(std::vector<T>& v, size_t n, hipStream_t s) const {
-        v.resize(n);
-        return n ? hipMemcpyAsync(v.data(), p, sizeof(T) * n, hipMemcpyDeviceToHost, s) : hipSuccess;
-    }
-};
-
-double seconds_since(std::chrono::steady_clock::time_point t) {
-    return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
-}
-
-using Sink = std::function<bool(const char*, size_t)>;
 
 const char kNuc[] = "-ACMGRSVTWYHKDBN";
 
@@ -187,13 +150,9 @@ int write_paths(pm_ctx* c, const ReplayState& r, const Paths& ph, const Sink& si
     const int32_t L = (int32_t)r.leaves.size();
     hipStream_t st = c->stream;
     hipError_t e = hipSuccess;
-    std::vector<int64_t> name_off(L + 1, 0);
+    std::vector<int64_t> name_off;
     std::vector<char> names;
-    for (int32_t li = 0; li < L; ++li) {
-        const std::string& nm = r.names[r.leaves[li]];
-        names.insert(names.end(), nm.begin(), nm.end());
-        name_off[li + 1] = (int64_t)names.size();
-    }
+    tip_names(r, name_off, names);
     Dev<int64_t> d_name_off, d_step_len, d_step_off, d_line_len, d_line_off;
     Dev<char> d_names;
     if (d_name_off.put(name_off, st) != hipSuccess || d_names.put(names, st) != hipSuccess ||
@@ -215,44 +174,28 @@ int write_paths(pm_ctx* c, const ReplayState& r, const Paths& ph, const Sink& si
     t.line_len = d_line_len.p;
     auto t0 = std::chrono::steady_clock::now();
     std::vector<int64_t> len;
-    if ((e = launch_gfa_step_len(c, t)) != hipSuccess || (e = maf_scan(c, d_step_len.p, d_step_off.p, ph.steps + 1)) != hipSuccess ||
+    if ((e = launch_gfa_step_len(c, t)) != hipSuccess || (e = exclusive_scan(c, d_step_len.p, d_step_off.p, ph.steps + 1)) != hipSuccess ||
         (e = launch_gfa_line_len(c, t)) != hipSuccess || (e = d_line_len.get(len, (size_t)L, st)) != hipSuccess ||
         (e = hipStreamSynchronize(st)) != hipSuccess)
         return hip_fail(c, e, "GFA line lengths");
-    // batches of whole lines: tips [t0, t1) under the byte limit (at least one line)
-    struct Batch {
-        int32_t t0, t1;
-        int64_t bytes;
-    };
-    std::vector<Batch> batches;
-    for (int32_t b0 = 0; b0 < L;) {
-        int32_t b1 = b0 + 1;
-        int64_t bytes = len[(size_t)b0];
-        while (b1 < L && bytes + len[(size_t)b1] <= c->gfa_batch_bytes) bytes += len[(size_t)b1++];
-        batches.push_back({b0, b1, bytes});
-        b0 = b1;
-    }
-    int32_t most = 0;
-    for (const Batch& b : batches) most = std::max(most, b.t1 - b.t0);
+    // batches of whole lines: tips under the byte limit (at least one line)
+    const std::vector<Batch> batches = cut_batches(len, c->gfa_batch_bytes);
+    int64_t most = 0;
+    for (const Batch& b : batches) most = std::max(most, b.i1 - b.i0);
     if (d_line_off.alloc((size_t)most, false, st) != hipSuccess) return fail(c, PM_ERR_OOM, "GFA line offsets");
     double t_text = seconds_since(t0), t_down = 0.0;
     for (const Batch& b : batches) {
         t0 = std::chrono::steady_clock::now();
         if (grow_device(&c->text_buf, &c->text_cap, (size_t)std::max<int64_t>(b.bytes, 1)) != hipSuccess)
             return fail(c, PM_ERR_OOM, "GFA text");
-        if ((e = maf_scan(c, d_line_len.p + b.t0, d_line_off.p, b.t1 - b.t0)) != hipSuccess ||
-            (e = launch_gfa_write(c, t, b.t0, b.t1, d_line_off.p, static_cast<char*>(c->text_buf),
-                                  (int64_t)ph.tip_off_host[(size_t)b.t1] - ph.tip_off_host[(size_t)b.t0])) != hipSuccess ||
+        if ((e = exclusive_scan(c, d_line_len.p + b.i0, d_line_off.p, b.i1 - b.i0)) != hipSuccess ||
+            (e = launch_gfa_write(c, t, (int32_t)b.i0, (int32_t)b.i1, d_line_off.p, static_cast<char*>(c->text_buf),
+                                  (int64_t)ph.tip_off_host[(size_t)b.i1] - ph.tip_off_host[(size_t)b.i0])) != hipSuccess ||
             (e = hipStreamSynchronize(st)) != hipSuccess)
             return hip_fail(c, e, "GFA text kernel");
         t_text += seconds_since(t0);
-        t0 = std::chrono::steady_clock::now();
-        bool wrote = true;
-        if (b.bytes && (e = d2h_stream(c, c->text_buf, (size_t)b.bytes, sink, wrote)) != hipSuccess)
-            return hip_fail(c, e, "GFA download");
-        if (!wrote) return fail(c, PM_ERR_ARG, "GFA write: " + std::string(std::strerror(errno)));
-        t_down += seconds_since(t0);
-        written += b.bytes;
+        const int rc = stream_text(c, "GFA", b.bytes, sink, written, t_down);
+        if (rc != PM_OK) return rc;
     }
     phase_add("gfa.text", t_text);
     phase_add("gfa.download_write", t_down);
@@ -327,12 +270,7 @@ int chunk_graph(pm_ctx* c, const ReplayState& r, PhaseClock& clock, std::string&
     const int32_t M = r.max_id + 1;
     if (r.columns >= (int64_t)1 << 31) return fail(c, PM_ERR_UNSUPPORTED, "GFA rows of 2^31 columns and more");
     // ---- host tables: held / strand per (tip, block); per block its chunks and their start codes
-    std::vector<uint8_t> held((size_t)L * M, 0);
-    host_parallel_for((L + 63) / 64, [&](int task) {
-        for (int32_t li = task * 64; li < std::min(L, task * 64 + 64); ++li)
-            for (int32_t id = 0; id < M; ++id)
-                if (r.exists[li][id]) held[(size_t)li * M + id] = (uint8_t)(kMafHeld | (r.strand[li][id] ? kMafForward : 0));
-    });
+    const std::vector<uint8_t> held = held_table(r);
     std::vector<int32_t> chunk_off(M + 1, 0), chunk_blk;
     for (int32_t id = 0; id < M; ++id) {
         const int64_t n = r.is_block[id] ? gfa_chunks(r.width[id]) : 0;
@@ -386,7 +324,7 @@ int chunk_graph(pm_ctx* c, const ReplayState& r, PhaseClock& clock, std::string&
     a.key = d_key.p;
     a.flag = d_flag.p;
     int64_t last[2] = {0, 0};   // the scan and the flag of the last item
-    if ((e = launch_gfa_chunk(c, a)) != hipSuccess || (e = maf_scan(c, d_flag.p, d_scan.p, items)) != hipSuccess ||
+    if ((e = launch_gfa_chunk(c, a)) != hipSuccess || (e = exclusive_scan(c, d_flag.p, d_scan.p, items)) != hipSuccess ||
         (items && ((e = hipMemcpyAsync(&last[0], d_scan.p + items - 1, sizeof(int64_t), hipMemcpyDeviceToHost, st)) != hipSuccess ||
                    (e = hipMemcpyAsync(&last[1], d_flag.p + items - 1, sizeof(int64_t), hipMemcpyDeviceToHost, st)) != hipSuccess)) ||
         (e = hipStreamSynchronize(st)) != hipSuccess)
@@ -417,7 +355,7 @@ int chunk_graph(pm_ctx* c, const ReplayState& r, PhaseClock& clock, std::string&
     int64_t tail[2] = {0, 0};
     if ((e = launch_gfa_compact(c, a, d_scan.p, s)) != hipSuccess || (e = gfa_sort(c, s, d_perm.p, d_scratch.p)) != hipSuccess ||
         (e = launch_gfa_heads(c, s, d_perm.p, d_head.p, d_creator.p)) != hipSuccess ||
-        (e = maf_scan(c, d_head.p, d_hscan.p, S)) != hipSuccess || (e = maf_scan(c, d_creator.p, d_cscan.p, S)) != hipSuccess ||
+        (e = exclusive_scan(c, d_head.p, d_hscan.p, S)) != hipSuccess || (e = exclusive_scan(c, d_creator.p, d_cscan.p, S)) != hipSuccess ||
         (e = launch_gfa_runs(c, s, d_perm.p, d_head.p, d_hscan.p, d_run_first.p)) != hipSuccess ||
         (S && ((e = hipMemcpyAsync(&tail[0], d_cscan.p + S - 1, sizeof(int64_t), hipMemcpyDeviceToHost, st)) != hipSuccess ||
                (e = hipMemcpyAsync(&tail[1], d_creator.p + S - 1, sizeof(int64_t), hipMemcpyDeviceToHost, st)) != hipSuccess)) ||
@@ -478,10 +416,7 @@ int gfa_steps(pm_ctx* c, const pm_panmat* p, const Sink& sink, int64_t* length) 
     if (!p || p->num_nodes < 1 || !p->child_offsets || !p->names) return fail(c, PM_ERR_ARG, "bad arguments");
     (void)hipSetDevice(c->device);
     const int64_t nuc = p->nuc_mut_offsets ? p->nuc_mut_offsets[p->num_nodes] : 0;
-    // a mutation on a secondary block: the replayed rows are not getSequenceFromReference's (as pm_maf)
-    if (p->nuc_mut_secondary)
-        for (int64_t k = 0; k < nuc; ++k)
-            if (p->nuc_mut_secondary[k] != -1) return fail(c, PM_ERR_UNSUPPORTED, "secondary blocks");
+    if (has_secondary_mutation(p)) return fail(c, PM_ERR_UNSUPPORTED, "secondary blocks");
     const bool blocks_only = nuc == 0;   // (:6-13) no node has a nucleotide mutation
     if (blocks_only && p->block_mut_offsets)   // blockExistsGlobal has blocks.size() + 1 entries (:34)
         for (int64_t k = 0; k < p->block_mut_offsets[p->num_nodes]; ++k)
@@ -498,21 +433,13 @@ int gfa_steps(pm_ctx* c, const pm_panmat* p, const Sink& sink, int64_t* length) 
     const int built = blocks_only ? whole_blocks(c, p, r, head, ph) : chunk_graph(c, r, clock, head, ph);
     if (built != PM_OK) return built;
     int64_t written = 0;
-    if (!head.empty() && !sink(head.data(), head.size())) return fail(c, PM_ERR_ARG, "GFA write: " + std::string(std::strerror(errno)));
+    if (!head.empty() && !sink(head.data(), head.size())) return write_failed(c, "GFA");
     written += (int64_t)head.size();
     const int wrc = write_paths(c, r, ph, sink, written);
     if (wrc != PM_OK) return wrc;
     phase_add("gfa.text_bytes", (double)written);   // (a count)
     if (length) *length = written;
     return PM_OK;
-}
-
-int gfa_run(pm_ctx* c, const pm_panmat* p, const Sink& sink, int64_t* length) {
-    try {
-        return gfa_steps(c, p, sink, length);
-    } catch (const std::bad_alloc&) {
-        return fail(c, PM_ERR_OOM, "GFA host buffers");
-    }
 }
 
 }  // namespace
@@ -525,40 +452,13 @@ extern "C" {
 int pm_gfa_fd(pm_ctx* c, const pm_panmat* p, int fd, int64_t* length) {
     if (!c) return PM_ERR_ARG;
     if (fd < 0) return fail(c, PM_ERR_ARG, "bad file descriptor");
-    return gfa_run(c, p, [fd](const char* q, size_t n) { return write_all(fd, q, n); }, length);
+    return guarded(c, "GFA", [&]() { return gfa_steps(c, p, fd_sink(fd), length); });
 }
 
 int pm_gfa(pm_ctx* c, const pm_panmat* p, char** text, int64_t* length) {
     if (!c) return PM_ERR_ARG;
     if (!text || !length) return fail(c, PM_ERR_ARG, "bad arguments");
-    char* buf = nullptr;
-    size_t used = 0, cap = 0;
-    const int rc = gfa_run(
-        c, p,
-        [&](const char* q, size_t n) {
-            if (used + n + 1 > cap) {
-                const size_t want = std::max(used + n + 1, cap * 2);
-                char* grown = static_cast<char*>(std::realloc(buf, want));
-                if (!grown) {
-                    errno = ENOMEM;
-                    return false;
-                }
-                buf = grown;
-                cap = want;
-            }
-            std::memcpy(buf + used, q, n);
-            used += n;
-            return true;
-        },
-        length);
-    if (rc != PM_OK) {
-        std::free(buf);
-        return rc;
-    }
-    if (!buf && !(buf = static_cast<char*>(std::malloc(1)))) return fail(c, PM_ERR_OOM, "GFA host buffers");
-    buf[used] = 0;
-    *text = buf;
-    return PM_OK;
+    return collect_text(c, "GFA", text, [&](const Sink& sink) { return gfa_steps(c, p, sink, length); });
 }
 
 }  // extern "C"

@@ -19,7 +19,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "pm_bits.h"
-#include "pm_internal.h"
+#include "pm_dev.h"
 
 namespace pm {
 namespace {
@@ -151,15 +151,6 @@ __global__ __launch_bounds__(256) void k_gfa_ids(GfaSteps s, const uint32_t* per
     }
 }
 
-__device__ __forceinline__ int digits_of(uint32_t v) {
-    int d = 1;
-    while (v >= 10) {
-        v /= 10;
-        ++d;
-    }
-    return d;
-}
-
 __device__ __forceinline__ int32_t printed_of(const GfaText& t, int64_t s) { return t.printed[2 * (int64_t)t.id[s] + t.forward[s]]; }
 
 // "<id><+|->," per kept step; the line's last kept step prints no comma (k_gfa_line_len)
@@ -220,14 +211,6 @@ __global__ __launch_bounds__(256) void k_gfa_write(GfaText t, int32_t t0, int32_
     }
 }
 
-unsigned blocks_of(int64_t n, int per) { return (unsigned)std::max<int64_t>(1, (n + per - 1) / per); }
-
-template <class T>
-void release(T*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
 }  // namespace
 
 hipError_t launch_gfa_chunk(pm_ctx* c, const GfaArgs& a) {
@@ -253,12 +236,12 @@ hipError_t gfa_sort(pm_ctx* c, const GfaSteps& s, uint32_t* perm, uint64_t* scra
     uint64_t *ka = scratch, *kb = scratch + n;
     uint32_t *pa = reinterpret_cast<uint32_t*>(scratch + 2 * n), *pb = reinterpret_cast<uint32_t*>(scratch + 3 * n);
     const dim3 grid(blocks_of(n, 256));
-    void* tmp = nullptr;
+    Dev<char> tmp;
     size_t tmp_bytes = 0;
     hipcub::DoubleBuffer<uint64_t> keys(ka, kb);
     hipcub::DoubleBuffer<uint32_t> vals(pa, pb);
     hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys, vals, (int)n, 0, 64, c->stream);
-    if (e == hipSuccess) e = hipMalloc(&tmp, std::max<size_t>(tmp_bytes, 1));
+    if (e == hipSuccess) e = tmp.alloc(tmp_bytes, false, c->stream);
     timer_begin(c, 3);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_gfa_iota, grid, dim3(256), 0, c->stream, vals.Current(), n);
@@ -269,13 +252,12 @@ hipError_t gfa_sort(pm_ctx* c, const GfaSteps& s, uint32_t* perm, uint64_t* scra
                            keys.Current(), n);
         e = hipGetLastError();
         // the low piece of (start code << 32 | length) and the string pieces use all 64 bits
-        if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, keys, vals, (int)n, 0, 64, c->stream);
+        if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, keys, vals, (int)n, 0, 64, c->stream);
     }
     if (e == hipSuccess)
         e = hipMemcpyAsync(perm, vals.Current(), sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToDevice, c->stream);
     timer_end(c, 3);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    release(tmp);
     return e;
 }
 

@@ -448,7 +448,7 @@ int pm_warmup(int device) {
     if (e != hipSuccess || n == 0) return PM_ERR_HIP;
     if (device < 0 || device >= n) return PM_ERR_ARG;
     if ((e = hipSetDevice(device)) != hipSuccess) return PM_ERR_HIP;
-    for (auto warm : {warm_fitch, warm_sankoff, warm_fitch_nt, warm_sankoff_nt, warm_replay, warm_synth, warm_sort, warm_vcf, warm_maf, warm_gfa})
+    for (auto warm : {warm_fitch, warm_sankoff, warm_fitch_nt, warm_sankoff_nt, warm_replay, warm_synth, warm_sort, warm_scan, warm_vcf, warm_maf, warm_gfa})
         if ((e = warm()) != hipSuccess) return PM_ERR_HIP;
     // the runtime's first allocation and staged copies
     void* d = nullptr;

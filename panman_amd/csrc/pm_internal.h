@@ -426,6 +426,7 @@ hipError_t warm_sankoff_nt();
 hipError_t warm_replay();
 hipError_t warm_synth();
 hipError_t warm_sort();
+hipError_t warm_scan();
 hipError_t sort_records_to_host(pm_ctx* c, const std::vector<uint32_t>& counts, int64_t n, pm_mut* out);
 // (Re)build the S2 / S3 leaf layout after the leaf columns or the tree changed (no-op when
 // it is current or the tree has no S2 / S3 node).
@@ -470,6 +471,8 @@ bool write_all(int fd, const char* p, size_t n);   // write(2) until done; false
 // *buf grown (contents dropped) to hold `need` bytes
 hipError_t grow_device(void** buf, size_t* cap, size_t need);
 void free_hostio(pm_ctx* c);
+// out[0 .. n) = exclusive scan of in[0 .. n) on the device, in == out: in place (pm_scan.hip)
+hipError_t exclusive_scan(pm_ctx* c, const int64_t* in, int64_t* out, int64_t n);
 
 // replay kernels (pm_replay.hip)
 struct ReplayDev {
@@ -598,8 +601,6 @@ struct VcfArgs {
 hipError_t launch_vcf_classify(pm_ctx* c, const VcfArgs& a);            // ref, coord, planes, nstart, chain
 hipError_t launch_vcf_list(pm_ctx* c, const VcfArgs& a);                // ev_leaf / ev_col from the scanned nstart
 hipError_t launch_vcf_emit(pm_ctx* c, const VcfArgs& a, bool write);    // count, or records + pool
-// exclusive scan in place of v[0 .. n] (v[n] receives the total)
-hipError_t vcf_scan(pm_ctx* c, int64_t* v, int64_t n);
 // Genotype text of a batch of lines: cells (line in batch, sample, ALT index), per line the
 // host's prefix; line lengths, offsets and text on the device.
 struct VcfTextArgs {
@@ -650,8 +651,6 @@ constexpr int64_t kMafNarrow4 = 49, kMafNarrow16 = 241;
 hipError_t launch_maf_size(pm_ctx* c, const MafArgs& a, const int32_t* cls_blk, int32_t n, int lanes);
 hipError_t launch_maf_start(pm_ctx* c, const MafArgs& a);
 hipError_t launch_maf_line_len(pm_ctx* c, const MafArgs& a);
-// out[0 .. n) = exclusive scan of in[0 .. n)
-hipError_t maf_scan(pm_ctx* c, const int64_t* in, int64_t* out, int64_t n);
 // The text of the entries [e0, e1) at text + line_off[e - e0]; wg_off[k] = first workgroup of
 // rank rank0 + k's entries inside the batch (its tips x its chunks), wg_off[nr] = the grid.
 struct MafBatch {

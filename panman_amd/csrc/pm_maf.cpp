@@ -9,59 +9,22 @@
 // most), cuts the lines into batches of whole lines and streams each batch through the pinned
 // download slots.
 #include <algorithm>
-#include <cerrno>
 #include <cstdlib>
-#include <cstring>
 #include <map>
-#include <new>
 #include <string>
 #include <vector>
 
+#include "pm_dev.h"
 #include "pm_replay.h"
 
 namespace pm {
 namespace {
 
-template <class T>
-struct Dev {   // a device array released on scope exit
-    T* p = nullptr;
-    Dev() = default;
-    Dev(const Dev&) = delete;
-    Dev& operator=(const Dev&) = delete;
-    ~Dev() { reset(); }
-    void reset() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    hipError_t alloc(size_t n, bool zero, hipStream_t s) {
-        reset();
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), sizeof(T) * std::max<size_t>(n, 1));
-        if (e != hipSuccess) p = nullptr;
-        else if (zero) e = hipMemsetAsync(p, 0, sizeof(T) * std::max<size_t>(n, 1), s);
-        return e;
-    }
-    hipError_t put(const std::vector<T>& v, hipStream_t s) {
-        hipError_t e = alloc(v.size(), false, s);
-        if (e == hipSuccess && !v.empty()) e = hipMemcpyAsync(p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, s);
-        return e;
-    }
-};
-
-double seconds_since(std::chrono::steady_clock::time_point t) {
-    return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
-}
-
-using Sink = std::function<bool(const char*, size_t)>;
-
 int maf_steps(pm_ctx* c, const pm_panmat* p, const Sink& sink, int64_t* length) {
     if (!c) return PM_ERR_ARG;
     if (!p || p->num_nodes < 1 || !p->child_offsets || !p->names) return fail(c, PM_ERR_ARG, "bad arguments");
     (void)hipSetDevice(c->device);
-    // getBlockSequenceFromReference skips a mutation on a secondary block where the replay
-    // applies it to the primary block: the replayed rows are not the MAF's rows then
-    if (p->nuc_mut_secondary && p->nuc_mut_offsets)
-        for (int64_t k = 0; k < p->nuc_mut_offsets[p->num_nodes]; ++k)
-            if (p->nuc_mut_secondary[k] != -1) return fail(c, PM_ERR_UNSUPPORTED, "secondary blocks");
+    if (has_secondary_mutation(p)) return fail(c, PM_ERR_UNSUPPORTED, "secondary blocks");
 
     int rc = fasta_replay(c, p);
     if (rc != PM_OK) return rc;
@@ -73,24 +36,11 @@ int maf_steps(pm_ctx* c, const pm_panmat* p, const Sink& sink, int64_t* length) 
     if (r.columns > (int64_t)0x7fffffff - 64) return fail(c, PM_ERR_UNSUPPORTED, "MAF rows of 2^31 columns and more");
 
     // ---- host tables: per (tip, block) held / strand and the print order; the name table ---
-    std::vector<uint8_t> held((size_t)L * M, 0);
-    std::vector<int32_t> order((size_t)L * M);
-    host_parallel_for((L + 63) / 64, [&](int task) {
-        std::vector<int32_t> ord;
-        for (int32_t li = task * 64; li < std::min(L, task * 64 + 64); ++li) {
-            print_order(r, li, ord);
-            std::copy(ord.begin(), ord.end(), order.begin() + (size_t)li * M);
-            for (int32_t id = 0; id < M; ++id)
-                if (r.exists[li][id]) held[(size_t)li * M + id] = (uint8_t)(kMafHeld | (r.strand[li][id] ? kMafForward : 0));
-        }
-    });
-    std::vector<int64_t> name_off(L + 1, 0);
+    std::vector<int32_t> order;
+    const std::vector<uint8_t> held = held_table(r, &order);
+    std::vector<int64_t> name_off;
     std::vector<char> names;
-    for (int32_t li = 0; li < L; ++li) {
-        const std::string& nm = r.names[r.leaves[li]];
-        names.insert(names.end(), nm.begin(), nm.end());
-        name_off[li + 1] = (int64_t)names.size();
-    }
+    tip_names(r, name_off, names);
     // ---- blocks grouped by equal consensusSeq words, groups in the map's order (unsigned words,
     // a proper prefix first), blocks of a group in block-list order (maf.cpp:71-75, 144-146)
     std::map<std::vector<uint32_t>, std::vector<int32_t>> groups;
@@ -154,30 +104,16 @@ int maf_steps(pm_ctx* c, const pm_panmat* p, const Sink& sink, int64_t* length) 
         (e = launch_maf_start(c, a)) != hipSuccess || (e = hipStreamSynchronize(st)) != hipSuccess)
         return hip_fail(c, e, "MAF sizes");
     clock.lap("maf.size");
-    std::vector<int64_t> len((size_t)entries);
-    if ((e = launch_maf_line_len(c, a)) != hipSuccess ||
-        (entries && (e = hipMemcpyAsync(len.data(), d_len.p, sizeof(int64_t) * (size_t)entries, hipMemcpyDeviceToHost, st)) != hipSuccess) ||
+    std::vector<int64_t> len;
+    if ((e = launch_maf_line_len(c, a)) != hipSuccess || (e = d_len.get(len, (size_t)entries, st)) != hipSuccess ||
         (e = hipStreamSynchronize(st)) != hipSuccess)
         return hip_fail(c, e, "MAF line lengths");
-    // batches of whole lines: entries [e0, e1) under the byte limit (at least one entry) and the
-    // launch grid's limit
-    struct Batch {
-        int64_t e0, e1, bytes, wgs;
-    };
-    std::vector<Batch> batches;
+    // batches of whole lines: entries under the byte limit (at least one entry) and, by their
+    // workgroups, the launch grid's limit
     auto chunks_of = [&](int64_t entry) { return (int64_t)maf_chunks(r.width[rank_blk[(size_t)(entry / L)]]); };
-    for (int64_t e0 = 0; e0 < entries;) {
-        int64_t e1 = e0 + 1, bytes = len[(size_t)e0], wgs = chunks_of(e0);
-        while (e1 < entries && bytes + len[(size_t)e1] <= c->maf_batch_bytes && wgs + chunks_of(e1) <= (int64_t)0x7fffffff) {
-            bytes += len[(size_t)e1];
-            wgs += chunks_of(e1);
-            ++e1;
-        }
-        batches.push_back({e0, e1, bytes, wgs});
-        e0 = e1;
-    }
+    const std::vector<Batch> batches = cut_batches(len, c->maf_batch_bytes, chunks_of, (int64_t)0x7fffffff);
     int64_t most = 0;
-    for (const Batch& b : batches) most = std::max(most, b.e1 - b.e0);
+    for (const Batch& b : batches) most = std::max(most, b.i1 - b.i0);
     Dev<int64_t> d_off;
     if (d_off.alloc((size_t)most, false, st) != hipSuccess) return fail(c, PM_ERR_OOM, "MAF line offsets");
     clock.lap("maf.layout");
@@ -186,15 +122,14 @@ int maf_steps(pm_ctx* c, const pm_panmat* p, const Sink& sink, int64_t* length) 
     static const char kHead[] = "##maf version=1\n";
     int64_t written = 0;
     double t_text = 0.0, t_down = 0.0;
-    auto write_failed = [&]() { return fail(c, PM_ERR_ARG, "MAF write: " + std::string(std::strerror(errno))); };
-    if (!sink(kHead, sizeof kHead - 1)) return write_failed();
+    if (!sink(kHead, sizeof kHead - 1)) return write_failed(c, "MAF");
     written += (int64_t)sizeof kHead - 1;
     for (const Batch& b : batches) {
-        auto t0 = std::chrono::steady_clock::now();
-        const int32_t rank0 = (int32_t)(b.e0 / L), rank1 = (int32_t)((b.e1 - 1) / L);
+        const auto t0 = std::chrono::steady_clock::now();
+        const int32_t rank0 = (int32_t)(b.i0 / L), rank1 = (int32_t)((b.i1 - 1) / L);
         std::vector<int32_t> wg_off{0};
         for (int32_t k = rank0; k <= rank1; ++k) {
-            const int64_t first = std::max<int64_t>((int64_t)k * L, b.e0), last = std::min<int64_t>((int64_t)(k + 1) * L, b.e1);
+            const int64_t first = std::max<int64_t>((int64_t)k * L, b.i0), last = std::min<int64_t>((int64_t)(k + 1) * L, b.i1);
             wg_off.push_back((int32_t)(wg_off.back() + (last - first) * maf_chunks(r.width[rank_blk[(size_t)k]])));
         }
         Dev<int32_t> d_wg;
@@ -202,24 +137,18 @@ int maf_steps(pm_ctx* c, const pm_panmat* p, const Sink& sink, int64_t* length) 
             grow_device(&c->text_buf, &c->text_cap, (size_t)std::max<int64_t>(b.bytes, 1)) != hipSuccess)
             return fail(c, PM_ERR_OOM, "MAF text");
         MafBatch mb{};
-        mb.e0 = b.e0;
-        mb.e1 = b.e1;
+        mb.e0 = b.i0;
+        mb.e1 = b.i1;
         mb.rank0 = rank0;
         mb.nr = rank1 - rank0 + 1;
         mb.wg_off = d_wg.p;
         mb.line_off = d_off.p;
         mb.text = static_cast<char*>(c->text_buf);
-        if ((e = maf_scan(c, d_len.p + b.e0, d_off.p, b.e1 - b.e0)) != hipSuccess ||
+        if ((e = exclusive_scan(c, d_len.p + b.i0, d_off.p, b.i1 - b.i0)) != hipSuccess ||
             (e = launch_maf_write(c, a, mb, wg_off.back())) != hipSuccess || (e = hipStreamSynchronize(st)) != hipSuccess)
             return hip_fail(c, e, "MAF text kernel");
         t_text += seconds_since(t0);
-        t0 = std::chrono::steady_clock::now();
-        bool wrote = true;
-        if (b.bytes && (e = d2h_stream(c, c->text_buf, (size_t)b.bytes, sink, wrote)) != hipSuccess)
-            return hip_fail(c, e, "MAF download");
-        if (!wrote) return write_failed();
-        t_down += seconds_since(t0);
-        written += b.bytes;
+        if ((rc = stream_text(c, "MAF", b.bytes, sink, written, t_down)) != PM_OK) return rc;
     }
     phase_add("maf.text", t_text);
     phase_add("maf.download_write", t_down);
@@ -227,14 +156,6 @@ int maf_steps(pm_ctx* c, const pm_panmat* p, const Sink& sink, int64_t* length) 
     phase_add("maf.entries", (double)entries);      // (block rank, tip) pairs, held or not
     if (length) *length = written;
     return PM_OK;
-}
-
-int maf_run(pm_ctx* c, const pm_panmat* p, const Sink& sink, int64_t* length) {
-    try {
-        return maf_steps(c, p, sink, length);
-    } catch (const std::bad_alloc&) {
-        return fail(c, PM_ERR_OOM, "MAF host buffers");
-    }
 }
 
 }  // namespace
@@ -247,39 +168,13 @@ extern "C" {
 int pm_maf_fd(pm_ctx* c, const pm_panmat* p, int fd, int64_t* length) {
     if (!c) return PM_ERR_ARG;
     if (fd < 0) return fail(c, PM_ERR_ARG, "bad file descriptor");
-    return maf_run(c, p, [fd](const char* q, size_t n) { return write_all(fd, q, n); }, length);
+    return guarded(c, "MAF", [&]() { return maf_steps(c, p, fd_sink(fd), length); });
 }
 
 int pm_maf(pm_ctx* c, const pm_panmat* p, char** text, int64_t* length) {
     if (!c) return PM_ERR_ARG;
     if (!text || !length) return fail(c, PM_ERR_ARG, "bad arguments");
-    char* buf = nullptr;
-    size_t used = 0, cap = 0;
-    const int rc = maf_run(
-        c, p,
-        [&](const char* q, size_t n) {
-            if (used + n + 1 > cap) {
-                const size_t want = std::max(used + n + 1, cap * 2);
-                char* grown = static_cast<char*>(std::realloc(buf, want));
-                if (!grown) {
-                    errno = ENOMEM;
-                    return false;
-                }
-                buf = grown;
-                cap = want;
-            }
-            std::memcpy(buf + used, q, n);
-            used += n;
-            return true;
-        },
-        length);
-    if (rc != PM_OK) {
-        std::free(buf);
-        return rc;
-    }
-    buf[used] = 0;
-    *text = buf;
-    return PM_OK;
+    return collect_text(c, "MAF", text, [&](const Sink& sink) { return maf_steps(c, p, sink, length); });
 }
 
 }  // extern "C"

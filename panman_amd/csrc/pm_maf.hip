@@ -13,10 +13,8 @@
 //   k_maf_write     one workgroup per (line, kMafChunk body bytes): prefix, body with x -> -,
 //                   16-byte non-temporal stores on the text's own 16-byte grid
 // Only vector stores and ordinary atomics.
-#include <hipcub/hipcub.hpp>
-
 #include "pm_bits.h"
-#include "pm_internal.h"
+#include "pm_dev.h"
 
 namespace pm {
 namespace {
@@ -108,15 +106,6 @@ __global__ __launch_bounds__(256) void k_maf_start(MafArgs a) {
         carry += round;
     }
     if (lane == 0) a.src_size[tip] = (int32_t)total;
-}
-
-__device__ __forceinline__ int digits_of(uint32_t v) {
-    int d = 1;
-    while (v >= 10) {
-        v /= 10;
-        ++d;
-    }
-    return d;
 }
 
 __device__ __forceinline__ int signed_width(int32_t v) {
@@ -291,8 +280,6 @@ __global__ __launch_bounds__(256) void k_maf_write(MafArgs a, MafBatch bt) {
     }
 }
 
-unsigned blocks_of(int64_t n, int per) { return (unsigned)std::max<int64_t>(1, (n + per - 1) / per); }
-
 }  // namespace
 
 hipError_t launch_maf_size(pm_ctx* c, const MafArgs& a, const int32_t* cls_blk, int32_t n, int lanes) {
@@ -324,22 +311,6 @@ hipError_t launch_maf_line_len(pm_ctx* c, const MafArgs& a) {
     hipLaunchKernelGGL(k_maf_line_len, dim3(blocks_of(entries, 256)), dim3(256), 0, c->stream, a);
     timer_end(c, 3);
     return hipGetLastError();
-}
-
-hipError_t maf_scan(pm_ctx* c, const int64_t* in, int64_t* out, int64_t n) {
-    if (n == 0) return hipSuccess;
-    void* tmp = nullptr;
-    size_t bytes = 0;
-    hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, (int)n, c->stream);
-    if (e == hipSuccess) e = hipMalloc(&tmp, std::max<size_t>(bytes, 1));
-    if (e == hipSuccess) {
-        timer_begin(c, 3);
-        e = hipcub::DeviceScan::ExclusiveSum(tmp, bytes, in, out, (int)n, c->stream);
-        timer_end(c, 3);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (tmp) (void)hipFree(tmp);
-    return e;
 }
 
 hipError_t launch_maf_write(pm_ctx* c, const MafArgs& a, const MafBatch& b, int32_t workgroups) {

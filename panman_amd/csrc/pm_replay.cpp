@@ -22,6 +22,7 @@
 #include <thread>
 #include <vector>
 
+#include "pm_dev.h"
 #include "pm_replay.h"
 
 namespace pm {
@@ -679,43 +680,29 @@ int format_device(pm_ctx* c, int aligned, int64_t& total, PhaseClock& clock, std
         }
     }
     });
-    std::vector<int64_t> name_off(L + 1, 0);
-    std::string names;
-    for (int32_t li = 0; li < L; ++li) {
-        names += r.names[r.leaves[li]];
-        name_off[li + 1] = (int64_t)names.size();
-    }
+    std::vector<int64_t> name_off;
+    std::vector<char> names;
+    tip_names(r, name_off, names);
     const size_t NS = (size_t)L * M;
-    FmtSeg* d_seg = nullptr;
-    int64_t *d_len = nullptr, *d_off = nullptr, *d_line = nullptr, *d_start = nullptr, *d_text_off = nullptr,
-            *d_name_off = nullptr;
-    char *d_names = nullptr, *d_text = nullptr;   // (d_text: the context's grow-only text buffer)
-    auto cleanup = [&]() {
-        dfree(d_seg); dfree(d_len); dfree(d_off); dfree(d_line); dfree(d_start); dfree(d_text_off);
-        dfree(d_name_off); dfree(d_names);
-    };
+    Dev<FmtSeg> d_seg;
+    Dev<int64_t> d_len, d_off, d_line, d_start, d_text_off, d_name_off;
+    Dev<char> d_names;
+    hipStream_t st = c->stream;
     clock.lap("fasta.segments_host");
-    hipError_t e = dput(&d_seg, seg, c->stream);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_len), sizeof(int64_t) * std::max<size_t>(NS, 1));
-    if (e != hipSuccess) {
-        cleanup();
+    hipError_t e = hipSuccess;
+    if ((e = d_seg.put(seg, st)) != hipSuccess || (e = d_len.alloc(NS, false, st)) != hipSuccess)
         return fail(c, PM_ERR_OOM, "FASTA segments");
-    }
     FmtArgs f{};
     f.rows = r.d_rows;
     f.row_stride = r.dev.row_stride;
     f.positions = M;
     f.aligned = aligned != 0;
-    f.seg = d_seg;
-    f.seg_len = d_len;
-    std::vector<int64_t> len(NS);
-    e = launch_fmt_count(c, f, L);
-    if (e == hipSuccess && NS) e = hipMemcpyAsync(len.data(), d_len, sizeof(int64_t) * NS, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        cleanup();
+    f.seg = d_seg.p;
+    f.seg_len = d_len.p;
+    std::vector<int64_t> len;
+    if ((e = launch_fmt_count(c, f, L)) != hipSuccess || (e = d_len.get(len, NS, st)) != hipSuccess ||
+        (e = hipStreamSynchronize(st)) != hipSuccess)
         return hip_fail(c, e, "FASTA segment count");
-    }
     std::vector<int64_t> off(NS), line(L), start(L), text_off(L + 1, 0);
     for (int32_t li = 0; li < L; ++li) {
         int64_t p = 0;
@@ -738,28 +725,60 @@ int format_device(pm_ctx* c, int aligned, int64_t& total, PhaseClock& clock, std
     }
     if (row_len) *row_len = line;
     clock.lap("fasta.count");
-    if ((e = dput(&d_off, off, c->stream)) != hipSuccess || (e = dput(&d_line, line, c->stream)) != hipSuccess ||
-        (e = dput(&d_start, start, c->stream)) != hipSuccess || (e = dput(&d_text_off, text_off, c->stream)) != hipSuccess ||
-        (e = dput(&d_name_off, name_off, c->stream)) != hipSuccess ||
-        (e = dput(&d_names, std::vector<char>(names.begin(), names.end()), c->stream)) != hipSuccess ||
-        (e = grow_device(&c->text_buf, &c->text_cap, (size_t)std::max<int64_t>(total, 1))) != hipSuccess) {
-        cleanup();
+    if ((e = d_off.put(off, st)) != hipSuccess || (e = d_line.put(line, st)) != hipSuccess ||
+        (e = d_start.put(start, st)) != hipSuccess || (e = d_text_off.put(text_off, st)) != hipSuccess ||
+        (e = d_name_off.put(name_off, st)) != hipSuccess || (e = d_names.put(names, st)) != hipSuccess ||
+        (e = grow_device(&c->text_buf, &c->text_cap, (size_t)std::max<int64_t>(total, 1))) != hipSuccess)
         return fail(c, PM_ERR_OOM, "FASTA buffers");
-    }
-    d_text = static_cast<char*>(c->text_buf);
-    f.seg_off = d_off;
-    f.line_len = d_line;
-    f.start = d_start;
-    f.text_off = d_text_off;
-    f.name_off = d_name_off;
-    f.names = d_names;
-    f.text = d_text;
+    f.seg_off = d_off.p;
+    f.line_len = d_line.p;
+    f.start = d_start.p;
+    f.text_off = d_text_off.p;
+    f.name_off = d_name_off.p;
+    f.names = d_names.p;
+    f.text = static_cast<char*>(c->text_buf);   // (the context's grow-only text buffer)
     e = launch_fmt_write(c, f, L);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
     clock.lap("fasta.text_kernel");
-    cleanup();
     if (e != hipSuccess) return hip_fail(c, e, "FASTA text kernel");
     return PM_OK;
+}
+
+void tip_names(const ReplayState& r, std::vector<int64_t>& name_off, std::vector<char>& names) {
+    const int32_t L = (int32_t)r.leaves.size();
+    name_off.assign(L + 1, 0);
+    names.clear();
+    for (int32_t li = 0; li < L; ++li) {
+        const std::string& nm = r.names[r.leaves[li]];
+        names.insert(names.end(), nm.begin(), nm.end());
+        name_off[li + 1] = (int64_t)names.size();
+    }
+}
+
+std::vector<uint8_t> held_table(const ReplayState& r, std::vector<int32_t>* order) {
+    const int32_t L = (int32_t)r.leaves.size();
+    const int32_t M = r.max_id + 1;
+    std::vector<uint8_t> held((size_t)L * M, 0);
+    if (order) order->resize((size_t)L * M);
+    host_parallel_for((L + 63) / 64, [&](int task) {
+        std::vector<int32_t> ord;
+        for (int32_t li = task * 64; li < std::min(L, task * 64 + 64); ++li) {
+            if (order) {
+                print_order(r, li, ord);
+                std::copy(ord.begin(), ord.end(), order->begin() + (size_t)li * M);
+            }
+            for (int32_t id = 0; id < M; ++id)
+                if (r.exists[li][id]) held[(size_t)li * M + id] = (uint8_t)(kMafHeld | (r.strand[li][id] ? kMafForward : 0));
+        }
+    });
+    return held;
+}
+
+bool has_secondary_mutation(const pm_panmat* p) {
+    if (!p->nuc_mut_secondary || !p->nuc_mut_offsets) return false;
+    for (int64_t k = 0; k < p->nuc_mut_offsets[p->num_nodes]; ++k)
+        if (p->nuc_mut_secondary[k] != -1) return true;
+    return false;
 }
 }  // namespace pm
 
@@ -808,7 +827,7 @@ int pm_replay_format(pm_ctx* c, int aligned, char** text, int64_t* length) {
     if (!c || !text || !length) return PM_ERR_ARG;
     PhaseClock clock;
     int64_t total = 0;
-    int rc = format_device(c, aligned, total, clock);
+    int rc = guarded(c, "FASTA", [&]() { return format_device(c, aligned, total, clock); });
     if (rc != PM_OK) return rc;
     char* out = static_cast<char*>(host_alloc_large((size_t)total + 1));
     if (!out) return fail(c, PM_ERR_OOM, "FASTA text");
@@ -829,13 +848,12 @@ int pm_replay_format_fd(pm_ctx* c, int aligned, int fd, int64_t* length) {
     if (!c || fd < 0) return PM_ERR_ARG;
     PhaseClock clock;
     int64_t total = 0;
-    int rc = format_device(c, aligned, total, clock);
+    int rc = guarded(c, "FASTA", [&]() { return format_device(c, aligned, total, clock); });
     if (rc != PM_OK) return rc;
-    bool wrote = true;
-    const hipError_t e = d2h_stream(c, c->text_buf, (size_t)total,
-                                    [fd](const char* p, size_t n) { return write_all(fd, p, n); }, wrote);
-    if (e != hipSuccess) return hip_fail(c, e, "FASTA download");
-    if (!wrote) return fail(c, PM_ERR_ARG, "FASTA write: " + std::string(std::strerror(errno)));
+    int64_t written = 0;
+    double t_down = 0.0;   // (logged by the clock, which carries on from the text kernel)
+    rc = stream_text(c, "FASTA", total, fd_sink(fd), written, t_down);
+    if (rc != PM_OK) return rc;
     clock.lap("fasta.download_write");
     if (length) *length = total;
     return PM_OK;
@@ -866,13 +884,13 @@ int fasta_replay(pm_ctx* c, const pm_panmat* p) {
 extern "C" {
 
 int pm_fasta_fd(pm_ctx* c, const pm_panmat* p, int aligned, int fd, int64_t* length) {
-    int rc = fasta_replay(c, p);
+    int rc = guarded(c, "FASTA", [&]() { return fasta_replay(c, p); });
     if (rc == PM_OK) rc = pm_replay_format_fd(c, aligned, fd, length);
     return rc;
 }
 
 int pm_fasta(pm_ctx* c, const pm_panmat* p, int aligned, char** text, int64_t* length) {
-    int rc = fasta_replay(c, p);
+    int rc = guarded(c, "FASTA", [&]() { return fasta_replay(c, p); });
     if (rc == PM_OK) rc = pm_replay_format(c, aligned, text, length);
     return rc;
 }
@@ -1008,8 +1026,7 @@ int pm_fasta_multi_fd(const pm_panmat* p, int aligned, const int* devices, int n
     for (int g = 0; g < G && status == PM_OK; ++g) {
         if (!ctx[g] || plen[g] == 0) continue;
         bool wrote = true;
-        const hipError_t e = d2h_stream(ctx[g], ctx[g]->text_buf, (size_t)plen[g],
-                                        [fd](const char* q, size_t n) { return write_all(fd, q, n); }, wrote);
+        const hipError_t e = d2h_stream(ctx[g], ctx[g]->text_buf, (size_t)plen[g], fd_sink(fd), wrote);
         if (e != hipSuccess) {
             set_err(std::string("FASTA download: ") + hipGetErrorString(e));
             status = PM_ERR_HIP;

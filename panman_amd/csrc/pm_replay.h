@@ -84,6 +84,14 @@ int replay_flatten(const pm_panmat* p, ReplayState& r, ReplayHost& h, int64_t le
 // (getSequenceFromReference(rotate = true), src/panman.cpp:4974-4999).  Shared by the FASTA
 // formatter and the MAF driver.
 void print_order(const ReplayState& r, int32_t li, std::vector<int32_t>& order);
+// The tips' names back to back: tip li's is names[name_off[li] .. name_off[li + 1]).
+void tip_names(const ReplayState& r, std::vector<int64_t>& name_off, std::vector<char>& names);
+// [tips][max_id + 1]: kMafHeld | kMafForward of a block the tip holds, 0 otherwise; `order`
+// (nullable) receives every tip's print_order in the same pass, [tips][max_id + 1].
+std::vector<uint8_t> held_table(const ReplayState& r, std::vector<int32_t>* order = nullptr);
+// A nucleotide mutation on a secondary block: getBlockSequenceFromReference skips it where the
+// replay applies it to the primary block, so the replayed rows are not the MAF's or the GFA's.
+bool has_secondary_mutation(const pm_panmat* p);
 // prepare + replay of every leaf (pm_fasta's first half); the rows stay in c->replay.
 int fasta_replay(pm_ctx* c, const pm_panmat* p);
 // The FASTA text of the replayed rows in c->text_buf (`total` bytes).  row_base / row_len

@@ -13,7 +13,7 @@
 #include <tuple>
 #include <vector>
 
-#include "pm_internal.h"
+#include "pm_dev.h"
 
 namespace pm {
 namespace {
@@ -49,15 +49,6 @@ __global__ __launch_bounds__(kBlock) void k_summary(const uint8_t* nuc_info, int
     }
 }
 
-template <class T>
-hipError_t to_device(const T* src, int64_t n, T** dst, hipStream_t s) {
-    *dst = nullptr;
-    if (n <= 0) return hipSuccess;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(dst), sizeof(T) * n);
-    if (e == hipSuccess) e = hipMemcpyAsync(*dst, src, sizeof(T) * n, hipMemcpyHostToDevice, s);
-    return e;
-}
-
 }  // namespace
 }  // namespace pm
 
@@ -70,26 +61,21 @@ extern "C" int pm_summary_compute(pm_ctx* c, const pm_panmat* p, pm_summary* out
     const int32_t N = p->num_nodes;
     const int64_t nuc_n = p->nuc_mut_offsets ? p->nuc_mut_offsets[N] : 0;
     const int64_t bm_n = p->block_mut_offsets ? p->block_mut_offsets[N] : 0;
-    uint8_t *d_nuc = nullptr, *d_bi = nullptr, *d_binv = nullptr;
-    unsigned long long* d_out = nullptr;
+    Dev<uint8_t> d_nuc, d_bi, d_binv;
+    Dev<unsigned long long> d_out;
     unsigned long long h[kSumCount] = {0, 0, 0, 0, 0, 0, 0};
-    hipError_t e = to_device(p->nuc_mut_info, nuc_n, &d_nuc, c->stream);
-    if (e == hipSuccess) e = to_device(p->block_mut_info, bm_n, &d_bi, c->stream);
-    if (e == hipSuccess) e = to_device(p->block_mut_inversion, bm_n, &d_binv, c->stream);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_out), sizeof h);
-    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, sizeof h, c->stream);
+    hipError_t e = d_nuc.put(p->nuc_mut_info, (size_t)nuc_n, c->stream);
+    if (e == hipSuccess) e = d_bi.put(p->block_mut_info, (size_t)bm_n, c->stream);
+    if (e == hipSuccess) e = d_binv.put(p->block_mut_inversion, (size_t)bm_n, c->stream);
+    if (e == hipSuccess) e = d_out.alloc(kSumCount, true, c->stream);
     if (e == hipSuccess && (nuc_n > 0 || bm_n > 0)) {
         const int64_t n = std::max(nuc_n, bm_n);
         const unsigned blocks = (unsigned)std::min<int64_t>(4096, (n + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(k_summary, dim3(blocks), dim3(kBlock), 0, c->stream, d_nuc, nuc_n, d_bi, d_binv, bm_n, d_out);
+        hipLaunchKernelGGL(k_summary, dim3(blocks), dim3(kBlock), 0, c->stream, d_nuc.p, nuc_n, d_bi.p, d_binv.p, bm_n, d_out.p);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(h, d_out, sizeof h, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h, d_out.p, sizeof h, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_nuc);
-    (void)hipFree(d_bi);
-    (void)hipFree(d_binv);
-    (void)hipFree(d_out);
     if (e != hipSuccess) return hip_fail(c, e, "summary reduction");
 
     // leaf depths in Newick leaf order (pre-order, children in list order), float sum as the

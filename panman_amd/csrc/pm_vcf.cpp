@@ -10,60 +10,19 @@
 // prefix; the genotype matrix and its text are produced on the device in batches of whole
 // lines and streamed through the pinned download slots.
 #include <algorithm>
-#include <cerrno>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <ctime>
-#include <new>
 #include <string>
 #include <string_view>
 #include <vector>
 
+#include "pm_dev.h"
 #include "pm_replay.h"
 
 namespace pm {
 namespace {
-
-template <class T>
-struct Dev {   // a device array released on scope exit
-    T* p = nullptr;
-    Dev() = default;
-    Dev(const Dev&) = delete;
-    Dev& operator=(const Dev&) = delete;
-    ~Dev() { reset(); }
-    void reset() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    hipError_t alloc(size_t n, bool zero, hipStream_t s) {
-        reset();
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), sizeof(T) * std::max<size_t>(n, 1));
-        if (e != hipSuccess) p = nullptr;
-        else if (zero) e = hipMemsetAsync(p, 0, sizeof(T) * std::max<size_t>(n, 1), s);
-        return e;
-    }
-    hipError_t put(const std::vector<T>& v, hipStream_t s) {
-        hipError_t e = alloc(v.size(), false, s);
-        if (e == hipSuccess && !v.empty()) e = hipMemcpyAsync(p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, s);
-        return e;
-    }
-};
-
-double seconds_since(std::chrono::steady_clock::time_point t) {
-    return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
-}
-
-int digits_of(uint64_t v) {
-    int d = 1;
-    while (v >= 10) {
-        v /= 10;
-        ++d;
-    }
-    return d;
-}
-
-using Sink = std::function<bool(const char*, size_t)>;
 
 int vcf_steps(pm_ctx* c, const pm_panmat* p, const char* reference, const Sink& sink, int64_t* length, int64_t* skipped) {
     if (!c) return PM_ERR_ARG;
@@ -155,7 +114,7 @@ int vcf_steps(pm_ctx* c, const pm_panmat* p, const char* reference, const Sink& 
         a.equal = d_equal.p;
         a.nstart = d_nstart.p;
         a.chain = d_chain.p;
-        if ((e = launch_vcf_classify(c, a)) != hipSuccess || (e = vcf_scan(c, d_nstart.p, L)) != hipSuccess ||
+        if ((e = launch_vcf_classify(c, a)) != hipSuccess || (e = exclusive_scan(c, d_nstart.p, d_nstart.p, (int64_t)L + 1)) != hipSuccess ||
             (e = hipMemcpy(&events, d_nstart.p + L, sizeof(int64_t), hipMemcpyDeviceToHost)) != hipSuccess)
             return hip_fail(c, e, "VCF classification");
         clock.lap("vcf.classify");
@@ -172,7 +131,8 @@ int vcf_steps(pm_ctx* c, const pm_panmat* p, const char* reference, const Sink& 
             a.ev_recs = d_erecs.p;
             a.ev_bytes = d_ebytes.p;
             if ((e = launch_vcf_list(c, a)) != hipSuccess || (e = launch_vcf_emit(c, a, false)) != hipSuccess ||
-                (e = vcf_scan(c, d_erecs.p, events)) != hipSuccess || (e = vcf_scan(c, d_ebytes.p, events)) != hipSuccess ||
+                (e = exclusive_scan(c, d_erecs.p, d_erecs.p, events + 1)) != hipSuccess ||
+                (e = exclusive_scan(c, d_ebytes.p, d_ebytes.p, events + 1)) != hipSuccess ||
                 (e = hipMemcpy(&nrec, d_erecs.p + events, sizeof(int64_t), hipMemcpyDeviceToHost)) != hipSuccess ||
                 (e = hipMemcpy(&nbytes, d_ebytes.p + events, sizeof(int64_t), hipMemcpyDeviceToHost)) != hipSuccess)
                 return hip_fail(c, e, "VCF event count");
@@ -297,13 +257,12 @@ int vcf_steps(pm_ctx* c, const pm_panmat* p, const char* reference, const Sink& 
     head += '\n';
     int64_t written = 0;
     double t_text = 0.0, t_down = 0.0;
-    auto write_failed = [&]() { return fail(c, PM_ERR_ARG, "VCF write: " + std::string(std::strerror(errno))); };
-    if (!sink(head.data(), head.size())) return write_failed();
+    if (!sink(head.data(), head.size())) return write_failed(c, "VCF");
     written += (int64_t)head.size();
-    for (int64_t l0 = 0; l0 < lines;) {
-        int64_t l1 = l0 + 1, bytes = est[(size_t)l0];
-        while (l1 < lines && bytes + est[(size_t)l1] <= c->vcf_batch_bytes && l1 - l0 < (int64_t)0x7fffffff) bytes += est[(size_t)l1++];
-        auto t0 = std::chrono::steady_clock::now();
+    // batches of whole lines under the byte limit by their bounds (at least one line) and the launch grid's limit
+    for (const Batch& b : cut_batches(est, c->vcf_batch_bytes, [](int64_t) { return (int64_t)1; }, (int64_t)0x7fffffff)) {
+        const int64_t l0 = b.i0, l1 = b.i1;
+        const auto t0 = std::chrono::steady_clock::now();
         const int64_t nl = l1 - l0, c0 = cell_off[(size_t)l0], nc = cell_off[(size_t)l1] - c0;
         std::vector<int32_t> bc(cells.begin() + 3 * c0, cells.begin() + 3 * (c0 + nc));
         for (int64_t k = 0; k < nc; ++k) bc[(size_t)(3 * k)] -= (int32_t)l0;
@@ -327,23 +286,17 @@ int vcf_steps(pm_ctx* c, const pm_panmat* p, const char* reference, const Sink& 
         t.prefix = d_pre.p;
         t.line_off = d_loff.p;
         int64_t total = 0;
-        if ((e = launch_vcf_text_count(c, t)) != hipSuccess || (e = vcf_scan(c, d_loff.p, nl)) != hipSuccess ||
+        if ((e = launch_vcf_text_count(c, t)) != hipSuccess || (e = exclusive_scan(c, d_loff.p, d_loff.p, nl + 1)) != hipSuccess ||
             (e = hipMemcpy(&total, d_loff.p + nl, sizeof(int64_t), hipMemcpyDeviceToHost)) != hipSuccess)
             return hip_fail(c, e, "VCF text count");
-        if (total > bytes) return fail(c, PM_ERR_STATE, "VCF text batch longer than its bound");
+        if (total > b.bytes) return fail(c, PM_ERR_STATE, "VCF text batch longer than its bound");
         if (grow_device(&c->text_buf, &c->text_cap, (size_t)std::max<int64_t>(total, 1)) != hipSuccess)
             return fail(c, PM_ERR_OOM, "VCF text");
         t.text = static_cast<char*>(c->text_buf);
         if ((e = launch_vcf_text_write(c, t)) != hipSuccess || (e = hipStreamSynchronize(st)) != hipSuccess)
             return hip_fail(c, e, "VCF text kernel");
         t_text += seconds_since(t0);
-        t0 = std::chrono::steady_clock::now();
-        bool wrote = true;
-        if ((e = d2h_stream(c, c->text_buf, (size_t)total, sink, wrote)) != hipSuccess) return hip_fail(c, e, "VCF download");
-        if (!wrote) return write_failed();
-        t_down += seconds_since(t0);
-        written += total;
-        l0 = l1;
+        if ((rc = stream_text(c, "VCF", total, sink, written, t_down)) != PM_OK) return rc;
     }
     phase_add("vcf.text", t_text);
     phase_add("vcf.download_write", t_down);
@@ -351,14 +304,6 @@ int vcf_steps(pm_ctx* c, const pm_panmat* p, const char* reference, const Sink& 
     if (length) *length = written;
     if (skipped) *skipped = skip_count;
     return PM_OK;
-}
-
-int vcf_run(pm_ctx* c, const pm_panmat* p, const char* reference, const Sink& sink, int64_t* length, int64_t* skipped) {
-    try {
-        return vcf_steps(c, p, reference, sink, length, skipped);
-    } catch (const std::bad_alloc&) {   // (138 M records at C5 are gigabytes of host vectors)
-        return fail(c, PM_ERR_OOM, "VCF host buffers");
-    }
 }
 
 }  // namespace
@@ -371,39 +316,14 @@ extern "C" {
 int pm_vcf_fd(pm_ctx* c, const pm_panmat* p, const char* reference, int fd, int64_t* length, int64_t* skipped) {
     if (!c) return PM_ERR_ARG;
     if (fd < 0) return fail(c, PM_ERR_ARG, "bad file descriptor");
-    return vcf_run(c, p, reference, [fd](const char* q, size_t n) { return write_all(fd, q, n); }, length, skipped);
+    // (138 M records at C5 are gigabytes of host vectors)
+    return guarded(c, "VCF", [&]() { return vcf_steps(c, p, reference, fd_sink(fd), length, skipped); });
 }
 
 int pm_vcf(pm_ctx* c, const pm_panmat* p, const char* reference, char** text, int64_t* length, int64_t* skipped) {
     if (!c) return PM_ERR_ARG;
     if (!text || !length) return fail(c, PM_ERR_ARG, "bad arguments");
-    char* buf = nullptr;
-    size_t used = 0, cap = 0;
-    const int rc = vcf_run(
-        c, p, reference,
-        [&](const char* q, size_t n) {
-            if (used + n + 1 > cap) {
-                const size_t want = std::max(used + n + 1, cap * 2);
-                char* grown = static_cast<char*>(std::realloc(buf, want));
-                if (!grown) {
-                    errno = ENOMEM;
-                    return false;
-                }
-                buf = grown;
-                cap = want;
-            }
-            std::memcpy(buf + used, q, n);
-            used += n;
-            return true;
-        },
-        length, skipped);
-    if (rc != PM_OK) {
-        std::free(buf);
-        return rc;
-    }
-    buf[used] = 0;
-    *text = buf;
-    return PM_OK;
+    return collect_text(c, "VCF", text, [&](const Sink& sink) { return vcf_steps(c, p, reference, sink, length, skipped); });
 }
 
 }  // extern "C"

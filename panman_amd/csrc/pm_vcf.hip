@@ -16,7 +16,8 @@
 // Only vector stores and ordinary atomics.
 #include <hipcub/hipcub.hpp>
 
-#include "pm_internal.h"
+#include "pm_bits.h"
+#include "pm_dev.h"
 
 namespace pm {
 namespace {
@@ -302,15 +303,6 @@ __global__ __launch_bounds__(256) void k_vcf_emit(VcfArgs a) {
 
 // ---- genotype text ------------------------------------------------------------------------
 
-__device__ __forceinline__ int digits_of(uint32_t v) {
-    int d = 1;
-    while (v >= 10) {
-        v /= 10;
-        ++d;
-    }
-    return d;
-}
-
 // (a tip with two ALTs of one line keeps the later one, as the reference's map assignment does)
 __global__ __launch_bounds__(256) void k_vcf_gt_fill(VcfTextArgs t) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -362,8 +354,6 @@ __global__ __launch_bounds__(256) void k_vcf_text_write(VcfTextArgs t) {
     if (threadIdx.x == 0) out[carry] = '\n';
 }
 
-unsigned blocks_of(int64_t n, int per) { return (unsigned)std::max<int64_t>(1, (n + per - 1) / per); }
-
 }  // namespace
 
 hipError_t launch_vcf_classify(pm_ctx* c, const VcfArgs& a) {
@@ -391,21 +381,6 @@ hipError_t launch_vcf_emit(pm_ctx* c, const VcfArgs& a, bool write) {
     else hipLaunchKernelGGL(k_vcf_emit<false>, dim3(blocks_of(a.events, 256)), dim3(256), 0, c->stream, a);
     timer_end(c, 3);
     return hipGetLastError();
-}
-
-hipError_t vcf_scan(pm_ctx* c, int64_t* v, int64_t n) {
-    void* tmp = nullptr;
-    size_t bytes = 0;
-    hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, v, v, (int)(n + 1), c->stream);
-    if (e == hipSuccess) e = hipMalloc(&tmp, std::max<size_t>(bytes, 1));
-    if (e == hipSuccess) {
-        timer_begin(c, 3);
-        e = hipcub::DeviceScan::ExclusiveSum(tmp, bytes, v, v, (int)(n + 1), c->stream);
-        timer_end(c, 3);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (tmp) (void)hipFree(tmp);
-    return e;
 }
 
 hipError_t launch_vcf_text_count(pm_ctx* c, const VcfTextArgs& t) {
