@@ -164,6 +164,9 @@ int pm_set_stream(pm_ctx* ctx, void* hip_stream);
  *   PM_OPT_GFA_IN_BATCH_SITES (default and most 2^24 - 1, the most sites pm_leaves_upload takes;
  *                  at least 1): pm_gfa_build uploads and runs the block columns in batches of at
  *                  most this many.  The result does not depend on it.
+ *   PM_OPT_SUBNET_BATCH_ENTRIES (default 2^25, 1 .. 2^31 - 2): pm_subnet expands, sorts and folds the merged
+ *                  chains' nucleotide mutations in batches of whole new nodes of at most this many bases (a node
+ *                  whose chain holds more gets a batch of its own).  The result does not depend on it.
  * (Option ids 1, 4, 5 and 11 -- subtree-region, heavy-path-chain and level-band schedules,
  * tail records overlapped with the pre-order levels -- were measured slower than, or no
  * faster than, the level kernels on MI355X and removed.) */
@@ -185,6 +188,7 @@ int pm_set_stream(pm_ctx* ctx, void* hip_stream);
 #define PM_OPT_GFA_BATCH_BYTES 21
 #define PM_OPT_DOWN_PACK 22
 #define PM_OPT_GFA_IN_BATCH_SITES 23
+#define PM_OPT_SUBNET_BATCH_ENTRIES 24
 int pm_set_option(pm_ctx* ctx, int option, int64_t value);
 /* Accumulate per-kernel-class device time with HIP events (see pm_kernel_times). */
 int pm_set_profiling(pm_ctx* ctx, int enable);
@@ -571,6 +575,32 @@ int pm_panman_write(const char* path, const pm_panmat* const* trees, int count, 
  * not hold -- although pm_fasta, like printFASTAUltraFastHelper, replays such a PanMAT (the
  * mutation lands on the primary block). */
 int pm_reroot(pm_ctx* ctx, const pm_panmat* tree, const char* leaf, pm_panman** out);
+
+/* Drop-in for Tree::subtreeExtractParallel(ids, {}) (src/subnet.cpp:3-135; the --subnet command,
+ * src/panmanUtils.cpp:584-652, through TreeGroup::subnetworkExtract, src/subnet.cpp:138-206): the tree cut down
+ * to the nodes named in `ids` (tips or internal nodes; duplicates do no harm).  Those nodes and all their
+ * ancestors are kept, with their child order; then every kept node with exactly one kept child is merged with
+ * it (compressTreeParallel, mergeNodes, src/panman.cpp:2033-2055), the root included: the merged node has the
+ * child's name and children, the sum of the branch lengths, consolidateNucMutations (src/panman.cpp:2233-2322)
+ * of the parent's list followed by the child's -- per coordinate the left fold of replaceMutation (:2058-2085),
+ * an insertion followed by a deletion removing the coordinate; the survivors sorted by (primary block,
+ * position, gap position) and regrouped into runs of at most 6 -- and consolidateBlockMutations (:2324-2372) of
+ * the two block lists, here in ascending block id (the reference's order is its hash map's).  A node that
+ * merges with nothing keeps its lists as they are.  A one-tip request gives a one-node tree.
+ * The result is a new one-tree pm_panman (in the pre-order of the new topology; release with pm_panman_free).
+ * Blocks and gaps are copied; a surviving node keeps the circular_offset, rotation_index and sequence_inverted
+ * of its surviving name (the reference also keeps those entries for dropped names: pm_panmat holds them per
+ * node, so they cannot be kept, and nothing reads them); branch_length NULL gives a result without lengths.
+ * Complex mutations are neither read nor written here, so nodeIdsToDefinitelyInclude is always empty.
+ * The merged chains' nucleotide mutations are consolidated on the GPU (profiling class 3) in batches
+ * (PM_OPT_SUBNET_BATCH_ENTRIES); a request that merges nothing launches nothing.  Phase log: subnet.*.
+ * Errors: num_ids == 0: PM_ERR_ARG; an unknown identifier: PM_ERR_ARG "Some of the specified node identifiers
+ * don't exist!!!"; on a merged chain, a nucleotide mutation with secondaryBlockId != -1: PM_ERR_UNSUPPORTED
+ * ("secondary blocks", as pm_reroot; on a node that merges with nothing it is copied), one outside its block or
+ * gap slots: PM_ERR_ARG, a block sequence the reference throws on (insertion after insertion, deletion or
+ * inversion after deletion, insertion after inversion): PM_ERR_ARG with the reference's message; blocks and gap
+ * slots of 2^32 coordinates or more in all: PM_ERR_UNSUPPORTED. */
+int pm_subnet(pm_ctx* ctx, const pm_panmat* tree, const char* const* ids, int64_t num_ids, pm_panman** out);
 
 /* Drop-in for Tree(pangraph.json, newick, FILE_TYPE::PANGRAPH, reference) (src/panman.cpp:
  * 820-1273; CLI -P/-N, src/panmanUtils.cpp:1364-1407): the PanGraph model

@@ -195,6 +195,19 @@ class Tree {
         index_ = 0;
     }
 
+    // Tree::subtreeExtractParallel(nodeIds, {}) + compressTreeParallel (src/subnet.cpp:3-135): the tree is
+    // replaced by the one cut down to `nodeIds` and their ancestors, unary chains merged.
+    void subnet(const std::vector<std::string>& nodeIds) {
+        detail::Ctx ctx(device_);
+        pm_panmat v = view();
+        std::vector<const char*> ids;
+        for (const std::string& id : nodeIds) ids.push_back(id.c_str());
+        pm_panman* out = nullptr;
+        ctx.check(pm_subnet(ctx.c, &v, ids.data(), (int64_t)ids.size(), &out), "pm_subnet");
+        file_ = detail::own(out);
+        index_ = 0;
+    }
+
     // Newick of the tree as stored (Tree::getNewickString, src/panman.cpp:1921-2029).
     std::string getNewickString() const { return pm_panman_newick(file_.get(), index_); }
 

@@ -1,6 +1,6 @@
 // panmanUtils-compatible command line for the GPU path (src/panmanUtils.cpp:128-182 option
 // table, :1302-1325 PanMAN load, :1409-1465 MSA build, :1326-1362 GFA build, :271-299 writePanMAN, :385-415 and
-// :458-490 FASTA / aligned FASTA, :699-732 GFA, :741-763 MAF, :766-786 Newick).  Only the commands on the accelerated
+// :458-490 FASTA / aligned FASTA, :584-652 subnetwork extraction, :699-732 GFA, :741-763 MAF, :766-786 Newick).  Only the commands on the accelerated
 // path are implemented; any other reference command is rejected with a message.
 #include <fcntl.h>
 #include <unistd.h>
@@ -54,6 +54,8 @@ const Spec kSpecs[] = {
     {"fasta-aligned", 'm', false, "Print MSA of sequences for each PanMAT in a PanMAN (FASTA format)"},
     {"maf", 'w', false, "Print m-WGA for each PanMAT in a PanMAN (MAF format)"},
     {"gfa", 'g', false, "Convert any PanMAT in a PanMAN to a GFA file"},
+    {"subnet", 'b', false, "Extract subnet of given PanMAN to a new PanMAN file based on the list of nodes provided in the input-file"},
+    {"input-file", 'i', true, "Path to the input file, required for --subnet (one line per tree: treeID id id ...)"},
     {"reroot", 'r', false, "Reroot a PanMAT in a PanMAN based on the input sequence id (--reference)"},
     {"treeID", 'd', true, "Tree ID, required for --reroot; the tree of --maf and --gfa (default 0)"},
     {"protobuf2capnp", 0, false, "Converts a Google Protobuf PanMAN (-I) to a Cap'n Proto PanMAN (-o)"},
@@ -68,7 +70,7 @@ const Spec kSpecs[] = {
 
 // Reference commands outside the accelerated path: recognised so the error is explicit.
 const char* const kOther[] = {"impute", "create-network", "printTips",
-                              "subnet", "vcf", "annotate",
+                              "vcf", "annotate",
                               "aa-translation", "extended-newick", "printMutations", "acr", "index",
                               "toUsher"};
 
@@ -263,6 +265,78 @@ int reroot(const Options& o, const pm_panman* file, int device) {
         return 1;
     }
     return 0;
+}
+
+// -I in.panman --subnet -i ids.txt -o out (src/panmanUtils.cpp:584-652): every tree cut down to the nodes its
+// line of the input file names ("treeID id id ..."), written as ./panman/<out>.panman.
+int subnet(const Options& o, const pm_panman* file, int device) {
+    if (!o.has("output-file")) {
+        print_error("Output file not provided!");
+        usage(std::cout);
+        return 1;
+    }
+    if (!o.has("input-file")) {
+        print_error("Input file not provided!");
+        usage(std::cout);
+        return 1;
+    }
+    std::ifstream in(o.get("input-file"));
+    if (!in) {
+        print_error("cannot read " + o.get("input-file"));
+        return 1;
+    }
+    const int trees = pm_panman_tree_count(file);
+    std::map<int, std::vector<std::string>> ids;
+    std::string line;
+    while (std::getline(in, line)) {
+        std::istringstream words(line);
+        std::string word;
+        if (!(words >> word)) continue;
+        std::vector<std::string>& list = ids[std::atoi(word.c_str())];
+        while (words >> word) list.push_back(word);
+    }
+    // (the reference would dereference a null root for a tree without a line)
+    for (int i = 0; i < trees; ++i)
+        if (!ids.count(i) || ids[i].empty()) {
+            print_error("no node identifiers for tree " + std::to_string(i) + " in " + o.get("input-file"));
+            return 1;
+        }
+    pm_ctx* ctx = nullptr;
+    if (pm_create(device, &ctx) != PM_OK) {
+        print_error("no HIP device");
+        return 1;
+    }
+    std::vector<pm_panman*> results(trees, nullptr);
+    std::vector<pm_panmat> views(trees);
+    std::vector<const pm_panmat*> list;
+    int status = 0;
+    const auto t0 = Clock::now();
+    for (int i = 0; i < trees && status == 0; ++i) {
+        pm_panmat view;
+        std::vector<const char*> names;
+        for (const std::string& id : ids[i]) names.push_back(id.c_str());
+        if (pm_panman_tree(file, i, &view) != PM_OK ||
+            pm_subnet(ctx, &view, names.data(), (int64_t)names.size(), &results[i]) != PM_OK) {
+            print_error(pm_last_error(ctx));
+            status = 1;
+            break;
+        }
+        pm_panman_tree(results[i], 0, &views[i]);
+        list.push_back(&views[i]);
+    }
+    if (status == 0) {   // (the reference's time covers the extraction and the write)
+        ::mkdir("./panman", 0777);
+        const std::string out = "./panman/" + o.get("output-file") + ".panman";
+        if (pm_panman_write(out.c_str(), list.data(), (int)list.size(), 1) != PM_OK) {
+            print_error("cannot write " + out);
+            status = 1;
+        } else {
+            std::cout << "\nParallel Subnetwork Extract execution time: " << ns_since(t0) << " nanoseconds\n";
+        }
+    }
+    for (pm_panman* r : results) pm_panman_free(r);
+    pm_destroy(ctx);
+    return status;
 }
 
 // -I in.panman --maf [--treeID k] [-o out] (src/panmanUtils.cpp:741-763): Tree::printMAF of one
@@ -480,6 +554,11 @@ int from_panman(const Options& o, const std::vector<int>& devices) {
     int status = 0;
     if (o.has("reroot")) {   // src/panmanUtils.cpp:855-892, then writePanMAN
         status = reroot(o, file, device);
+        pm_panman_free(file);
+        return status;
+    }
+    if (o.has("subnet")) {
+        status = subnet(o, file, device);
         pm_panman_free(file);
         return status;
     }

@@ -50,6 +50,12 @@ constexpr int kMaskWords = 8;     // record masks per (node, tile): complex, sim
                                   // Fitch: the first / second child's dirty lanes (one 64-B line)
 // The most sites one leaf upload takes (a record's site field is 24 bits; pm_leaves_upload).
 constexpr int64_t kMaxUploadSites = ((int64_t)1 << 24) - 1;
+// pm_subnet's default batch (PM_OPT_SUBNET_BATCH_ENTRIES), in expanded bases.  hipCUB takes its item count as an
+// int, so a batch must stay below 2^31; a base costs about 110 B of device memory across the pipeline (two
+// 8-B key and two 8-B value buffers, 12 B of coordinates, 9 B of fold results, then up to 33 B per survivor and
+// 17 B per record), and hipCUB's temporaries are histograms, independent of the count.  2^25 bases is 1 / 64 of
+// the int range and about 3.5 GiB, a small part of the device's memory.
+constexpr int64_t kSubnetBatchEntries = (int64_t)1 << 25;
 // Grouped post-order launches (PM_OPT_UP_GROUP): heights of at most this many nodes group.
 #ifndef PM_UP_GROUP_NODES
 #define PM_UP_GROUP_NODES 2048
@@ -395,6 +401,7 @@ struct pm_ctx {
     int64_t maf_batch_bytes = (int64_t)1 << 30;   // pm_maf: text per device batch of whole lines (PM_OPT_MAF_BATCH_BYTES)
     int64_t gfa_batch_bytes = (int64_t)1 << 30;   // pm_gfa: text per device batch of whole P lines (PM_OPT_GFA_BATCH_BYTES)
     int64_t gfa_in_batch_sites = pm::kMaxUploadSites; // pm_gfa_build: block columns per upload and run (PM_OPT_GFA_IN_BATCH_SITES)
+    int64_t subnet_batch_entries = pm::kSubnetBatchEntries;   // pm_subnet: expanded bases sorted per batch (PM_OPT_SUBNET_BATCH_ENTRIES)
 };
 
 namespace pm {
@@ -732,6 +739,70 @@ hipError_t launch_gfa_line_len(pm_ctx* c, const GfaText& t);
 hipError_t launch_gfa_write(pm_ctx* c, const GfaText& t, int32_t t0, int32_t t1, const int64_t* line_off, char* text,
                             int64_t batch_steps);
 hipError_t warm_gfa();
+// Subnetwork extraction (pm_subnet.hip; consolidateNucMutations, src/panman.cpp:2233-2322) over the
+// mutation records of the merged chains of one batch, in chain order (top first, list order within
+// a node).  A coordinate's rank in (primary, position, gap position) tuple order is
+// block_base[primary] + pos_base[pos_off[primary] + position] + gap position + 1.
+constexpr int32_t kSubnetBadBlock = 1, kSubnetBadPos = 2, kSubnetBadGap = 3, kSubnetUnstable = 4;   // SubnetArgs::error
+struct SubnetArgs {
+    int64_t records;
+    const int32_t* rec_node;       // [records] new node id
+    const int32_t* rec_primary;
+    const int32_t* rec_pos;
+    const int32_t* rec_gap;        // -1: main position
+    const uint8_t* rec_info;       // (length << 4) | type
+    const uint32_t* rec_nucs;
+    int32_t blocks;                // block ids 0 .. blocks - 1
+    const int32_t* blk_len;        // [blocks] main positions 0 .. len (the sentinel included); -1: no such block
+    const uint32_t* block_base;    // [blocks]
+    const int64_t* pos_off;        // [blocks] into pos_base
+    const uint32_t* pos_base;      // per block len + 2 entries: prefix of 1 + gap length at the position
+    int64_t* rec_off;              // [records + 1] bases per record, then their exclusive scan
+    int32_t* error;                // [1] the largest kSubnet* code met, 0: none
+};
+// One expanded base: key = new node << 32 | rank; val = entry number << 8 | SNP type << 4 | code.
+struct SubnetEntries {
+    int64_t n;
+    uint64_t* key;                 // [n]
+    uint64_t* val;                 // [n]
+    int32_t* blk;                  // [n] the coordinate, by entry number
+    int32_t* pos;
+    int32_t* gap;
+};
+hipError_t launch_subnet_count(pm_ctx* c, const SubnetArgs& a);
+hipError_t launch_subnet_expand(pm_ctx* c, const SubnetArgs& a, const SubnetEntries& e);
+// key / val sorted by key over bits [0, end_bit), stable: equal keys stay in entry order.  key_alt / val_alt: the
+// second halves of the double buffers; *key_out / *val_out: where the sorted arrays ended up.
+hipError_t subnet_sort(pm_ctx* c, const SubnetEntries& e, uint64_t* key_alt, uint64_t* val_alt, int end_bit, uint64_t** key_out,
+                       uint64_t** val_out);
+// alive[i] = 1 and tc[i] = type << 4 | code at the first entry of every key whose fold survives (alive: n + 1
+// entries, the last 0); launch_subnet_compact takes its exclusive scan
+hipError_t launch_subnet_fold(pm_ctx* c, const uint64_t* key, const uint64_t* val, int64_t n, int64_t* alive, uint8_t* tc,
+                              int32_t* error);
+// The survivors in sorted order (launch_subnet_compact).
+struct SubnetLive {
+    int64_t m;
+    int32_t* node;                 // [m]
+    int32_t* blk;
+    int32_t* pos;
+    int32_t* gap;
+    uint8_t* tc;                   // type << 4 | code
+    int64_t* head;                 // [m] own index at the head of a maximal run, else 0; then the nearest head
+    int64_t* start;                // [m + 1] 1: a record starts here; then the exclusive scan
+};
+hipError_t launch_subnet_compact(pm_ctx* c, const uint64_t* key, const uint64_t* val, int64_t n, const int64_t* ascan,
+                                 const uint8_t* tc, const SubnetEntries& e, const SubnetLive& s);
+hipError_t subnet_runs(pm_ctx* c, const SubnetLive& s);     // head (scanned) and start (flags)
+struct SubnetOut {
+    int32_t* primary;              // [records out]
+    int32_t* pos;
+    int32_t* gap;
+    uint8_t* info;
+    uint32_t* nucs;
+    int32_t* node_count;           // [new nodes] records per new node (zeroed by the caller)
+};
+hipError_t launch_subnet_pack(pm_ctx* c, const SubnetLive& s, const SubnetOut& o);
+hipError_t warm_subnet();
 // rows[leaf][c0 .. c0+n) chars -> packed codes out[leaf][(n+1)/2] ('-', 'x' -> 0)
 hipError_t launch_rows_to_codes(pm_ctx* c, const char* rows, int64_t row_stride, int32_t leaves, int64_t c0,
                                 int64_t n, uint8_t* out, int64_t out_stride);
