@@ -1,6 +1,5 @@
 // pm_chain.h -- what the PanGraph and GFA builders share: chain_align (src/chaining.cpp:285-310)
-// restated, the chained alignment of a path of block names against the running consensus order,
-// and the encoding of a block's consensus sequence.
+// restated, the chained alignment of a path of block names against the running consensus order.
 // Order-dependent steps follow the reference's containers (the score map is the same
 // std::unordered_map fed the same insertions, so libstdc++ iterates it in the same order).
 #pragma once
@@ -14,26 +13,6 @@
 #include <vector>
 
 namespace pm {
-
-inline uint8_t code_of(char ch) {
-    switch (ch) {
-        case 'A': return 1;  case 'C': return 2;  case 'G': return 4;  case 'T': return 8;
-        case 'R': return 5;  case 'Y': return 10; case 'S': return 6;  case 'W': return 9;
-        case 'K': return 12; case 'M': return 3;  case 'B': return 14; case 'D': return 13;
-        case 'H': return 11; case 'V': return 7;  case 'N': return 15;
-        default: return 0;
-    }
-}
-
-inline std::vector<uint32_t> encode_block(const std::string& seq) {   // Block(i, seq), src/panman.cpp:246-257
-    std::vector<uint32_t> w;
-    for (size_t i = 0; i < seq.size(); i += 8) {
-        uint32_t x = 0;
-        for (size_t j = i; j < std::min(i + 8, seq.size()); ++j) x ^= (uint32_t)code_of(seq[j]) << (4 * (7 - (j - i)));
-        w.push_back(x);
-    }
-    return w;
-}
 
 // ---- src/chaining.cpp -----------------------------------------------------------------
 using Pt = std::pair<int, int>;

@@ -1,16 +1,21 @@
 // pm_dev.h -- device-side plumbing shared by the extraction drivers (pm_replay.cpp's formatter,
 // pm_vcf, pm_maf, pm_gfa, pm_summary): a scoped device array, the grid size of a launch, the
-// download of a text batch into a sink and the wrappers of the C entry points.
+// download of a text batch into a sink and the wrappers of the C entry points; and by the
+// construction drivers (pm_msa, pm_pangraph, pm_gfa_in, pm_reroot, pm_subnet; their host-only
+// half is pm_build.h): the one-tree handle behind an entry point, a run over the uploaded columns
+// and the fetch of its records.
 #pragma once
 
 #include <algorithm>
 #include <cerrno>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
 
 #include "pm_internal.h"
+#include "pm_panman_tree.h"
 #include "pm_text.h"
 
 namespace pm {
@@ -83,6 +88,39 @@ int guarded(pm_ctx* c, const char* what, Run&& run) {
     } catch (const std::bad_alloc&) {
         return fail(c, PM_ERR_OOM, std::string(what) + " host buffers");
     }
+}
+
+// A handle-returning entry point over its driver: run(tree) fills the one tree of a new handle.
+// On failure the handle is released and *out stays null.
+template <class Run>
+int build_handle(pm_ctx* c, const char* what, pm_panman** out, Run&& run) {
+    *out = nullptr;
+    (void)hipSetDevice(c->device);
+    std::unique_ptr<pm_panman> res(new (std::nothrow) pm_panman());
+    if (!res) return fail(c, PM_ERR_OOM, std::string(what) + " host buffers");
+    const int rc = guarded(c, what, [&]() {
+        res->trees.resize(1);
+        return run(res->trees[0]);
+    });
+    if (rc == PM_OK) *out = res.release();
+    return rc;
+}
+
+// Every record of the last run, sorted by (node, site).
+inline int fetch_records(pm_ctx* c, std::vector<pm_mut>& recs) {
+    int64_t n = 0;
+    const int rc = pm_mutation_count(c, &n);
+    if (rc != PM_OK) return rc;
+    recs.resize((size_t)n);
+    return n ? pm_mutations_fetch(c, recs.data(), n, &n) : PM_OK;
+}
+
+// One pass over the uploaded leaf columns: the sites' packed root parent codes (and forced root
+// codes, or null), the run, the records.
+inline int run_columns(pm_ctx* c, int mode, const std::vector<uint8_t>& cons4, const uint8_t* forced4, std::vector<pm_mut>& recs) {
+    int rc;
+    if ((rc = pm_sites_upload(c, cons4.data(), forced4)) != PM_OK || (rc = pm_run(c, mode)) != PM_OK) return rc;
+    return fetch_records(c, recs);
 }
 
 // A buffer-returning entry point over its driver: run(sink) writes the text, *text receives it

@@ -15,10 +15,9 @@
 #include <utility>
 #include <vector>
 
+#include "pm_build.h"
 #include "pm_chain.h"
-#include "pm_internal.h"
-#include "pm_newick.h"
-#include "pm_panman_tree.h"
+#include "pm_dev.h"
 
 namespace pm {
 namespace {
@@ -29,18 +28,14 @@ struct GfaPath {
     std::vector<size_t> blocks;    // block id per step (GfaGraph::intSequences)
 };
 
-struct Stopwatch {
-    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-    double lap() {
-        const auto now = std::chrono::steady_clock::now();
-        const double s = std::chrono::duration<double>(now - t).count();
-        t = now;
-        return s;
-    }
-};
-
 int build(pm_ctx* c, const char* gfa_text, const char* newick_c, PanmanTree& out) {
-    Stopwatch watch;
+    // the phases are logged together at the end, and only by a build that succeeds
+    auto mark = std::chrono::steady_clock::now();
+    auto lap = [&](double& into) {
+        into += seconds_since(mark);
+        mark = std::chrono::steady_clock::now();
+    };
+    double t_parse = 0, t_chain = 0, t_upload = 0, t_run = 0, t_assemble = 0;
     // ---- parse (:729-753): "S" and "P" records, a later duplicate wins, anything else ignored
     std::map<std::string, std::string> nodes;
     std::map<std::string, std::vector<std::pair<std::string, bool>>> paths;
@@ -89,14 +84,11 @@ int build(pm_ctx* c, const char* gfa_text, const char* newick_c, PanmanTree& out
         path_name.push_back(p.first);
         gp.push_back(std::move(g));
     }
-    std::string newick(newick_c);
-    const size_t nl = newick.find('\n');
-    if (nl != std::string::npos) newick.resize(nl);
     Topology t;
     std::string err;
-    if (!parse_topology(newick, t, err)) return fail(c, PM_ERR_ARG, "Newick: " + err);
+    if (!parse_newick(newick_c, t, err)) return fail(c, PM_ERR_ARG, "Newick: " + err);
     const int32_t N = (int32_t)t.name.size();
-    const double t_parse = watch.lap();
+    lap(t_parse);
 
     // ---- block order (GfaGraph::GfaGraph, :6060-6142): the first path seeds the consensus, every
     // later one is chained against it; unmatched steps get fresh ids; ids renumbered at the end
@@ -155,24 +147,16 @@ int build(pm_ctx* c, const char* gfa_text, const char* newick_c, PanmanTree& out
             p1 = g.blocks[p2] + 1;
         }
     }
-    const double t_chain = watch.lap();
+    lap(t_chain);
 
-    pm_tree tree{};
-    std::vector<int32_t> off(N + 1, 0), idx;
-    for (int32_t v = 0; v < N; ++v) {
-        idx.insert(idx.end(), t.kids[v].begin(), t.kids[v].end());
-        off[v + 1] = (int32_t)idx.size();
-    }
-    tree.num_nodes = N;
-    tree.root = t.root;
-    tree.child_offsets = off.data();
-    tree.child_index = idx.data();
+    tree_from_topology(t, out);
+    const pm_tree tree = tree_view(out);
     int rc = pm_tree_upload(c, &tree);
     if (rc != PM_OK) return rc;
-    double t_upload = watch.lap(), t_run = 0;
+    lap(t_upload);
 
     // ---- block Fitch (:798-800), batches of columns
-    std::vector<std::vector<std::pair<int32_t, uint8_t>>> bmuts(N);
+    std::vector<std::vector<BlockRec>> bmuts(N);
     std::vector<size_t> cursor(R, 0);
     std::vector<int64_t> row_off(R + 1, 0);
     std::vector<int32_t> site;
@@ -191,31 +175,16 @@ int build(pm_ctx* c, const char* gfa_text, const char* newick_c, PanmanTree& out
             row_off[r + 1] = (int64_t)site.size();
         }
         const std::vector<uint8_t> cons_p((size_t)(S + 1) / 2, 0);   // root parent state: absent
-        if ((rc = pm_leaves_upload_sparse(c, S, R, row_off.data(), site.data(), code.data(), 0, node_row.data())) != PM_OK ||
-            (rc = pm_sites_upload(c, cons_p.data(), nullptr)) != PM_OK)
-            return rc;
-        t_upload += watch.lap();
-        int64_t n = 0;
-        if ((rc = pm_run(c, PM_MODE_BLOCK_FITCH)) != PM_OK || (rc = pm_mutation_count(c, &n)) != PM_OK) return rc;
-        std::vector<pm_mut> recs((size_t)n);
-        if (n && (rc = pm_mutations_fetch(c, recs.data(), n, &n)) != PM_OK) return rc;
+        if ((rc = pm_leaves_upload_sparse(c, S, R, row_off.data(), site.data(), code.data(), 0, node_row.data())) != PM_OK) return rc;
+        lap(t_upload);
+        std::vector<pm_mut> recs;
+        if ((rc = run_columns(c, PM_MODE_BLOCK_FITCH, cons_p, nullptr, recs)) != PM_OK) return rc;
         for (const pm_mut& m : recs)
             bmuts[m.node].emplace_back((int32_t)(c0 + (m.site_info >> 8)), (uint8_t)(m.site_info & 0xFF));
-        t_run += watch.lap();
+        lap(t_run);
     }
 
     // ---- the PanMAT: blocks Block(i, sequence) (:777-779); no gaps, no nucleotide mutations
-    out.num_nodes = N;
-    out.root = t.root;
-    out.child_off = off;
-    out.child_idx = idx;
-    out.names_blob.clear();
-    for (int32_t v = 0; v < N; ++v) {
-        out.names_blob += t.name[v];
-        out.names_blob.push_back('\0');
-    }
-    out.length = t.length;
-    out.newick = newick_of(t);
     out.block_seq_off.assign(1, 0);
     out.gap_off.assign(1, 0);
     for (size_t i = 0; i < T; ++i) {
@@ -224,27 +193,16 @@ int build(pm_ctx* c, const char* gfa_text, const char* newick_c, PanmanTree& out
         out.block_seq.insert(out.block_seq.end(), w.begin(), w.end());
         out.block_seq_off.push_back((int64_t)out.block_seq.size());
     }
-    out.bm_off.assign(N + 1, 0);
-    out.nm_off.assign(N + 1, 0);
     for (int32_t v = 0; v < N; ++v) {
-        auto& bl = bmuts[v];
-        std::sort(bl.begin(), bl.end());   // ascending block id (the reference's order is TBB-scheduled)
-        for (const auto& bm : bl) {        // src/fitchSankoff.cpp:279-303
-            const int type = bm.second >> 4, cd = bm.second & 15;
-            out.bm_primary.push_back(bm.first);
-            out.bm_info.push_back(type == PM_MUT_NI ? 1 : 0);
-            out.bm_inv.push_back(type == PM_MUT_NI ? cd == 2 : type == PM_MUT_NS);
-        }
-        out.bm_off[v + 1] = (int64_t)out.bm_primary.size();
+        std::sort(bmuts[v].begin(), bmuts[v].end());   // ascending block id (the reference's order is TBB-scheduled)
+        append_block_muts(out, v, bmuts[v]);
     }
-    out.circular.assign(N, -1);
-    out.rotation.assign(N, 0);
-    out.inverted.assign(N, 0);
+    lap(t_assemble);
     phase_add("gfain.parse", t_parse);
     phase_add("gfain.chain", t_chain);
     phase_add("gfain.upload", t_upload);
     phase_add("gfain.run", t_run);
-    phase_add("gfain.assemble", watch.lap());
+    phase_add("gfain.assemble", t_assemble);
     return PM_OK;
 }
 
@@ -253,15 +211,5 @@ int build(pm_ctx* c, const char* gfa_text, const char* newick_c, PanmanTree& out
 
 extern "C" int pm_gfa_build(pm_ctx* c, const char* gfa_text, const char* newick, pm_panman** out) {
     if (!c || !gfa_text || !newick || !out) return PM_ERR_ARG;
-    *out = nullptr;
-    (void)hipSetDevice(c->device);
-    auto* res = new pm_panman();
-    res->trees.resize(1);
-    const int rc = pm::build(c, gfa_text, newick, res->trees[0]);
-    if (rc != PM_OK) {
-        delete res;
-        return rc;
-    }
-    *out = res;
-    return PM_OK;
+    return pm::build_handle(c, "gfa build", out, [&](pm::PanmanTree& tree) { return pm::build(c, gfa_text, newick, tree); });
 }

@@ -17,21 +17,11 @@
 #include <thread>
 #include <vector>
 
-#include "pm_internal.h"
-#include "pm_newick.h"
+#include "pm_build.h"
+#include "pm_dev.h"
 
 namespace pm {
 namespace {
-
-int nuc_code(char c) {
-    switch (c) {
-        case 'A': return 1;  case 'C': return 2;  case 'G': return 4;  case 'T': return 8;
-        case 'R': return 5;  case 'Y': return 10; case 'S': return 6;  case 'W': return 9;
-        case 'K': return 12; case 'M': return 3;  case 'B': return 14; case 'D': return 13;
-        case 'H': return 11; case 'V': return 7;  case 'N': return 15;
-        default: return 0;   // gap, lowercase, anything else (src/panman.cpp:78-113)
-    }
-}
 
 // M1 reader: rows keyed (and ordered) by name, '\r' stripped, equal lengths required
 // (src/panman.cpp:1285-1322).
@@ -64,27 +54,6 @@ bool read_rows(const std::string& text, std::map<std::string, std::string>& rows
     return true;
 }
 
-struct Grouped {
-    int32_t pos;
-    uint32_t info;
-    uint32_t nucs;
-};
-
-// NucMut runs: a new record starts after 6 codes, at a position gap or a type change.
-void group_node(const pm_mut* r, int64_t n, std::vector<Grouped>& out) {
-    auto pos = [&](int64_t i) { return (int32_t)(r[i].site_info >> 8); };
-    auto typ = [&](int64_t i) { return (r[i].site_info >> 4) & 15u; };
-    int64_t start = 0;
-    auto emit = [&](int64_t a, int64_t b) {
-        Grouped g{pos(a), (uint32_t)(((b - a) << 4) + typ(a)), 0};
-        for (int64_t k = a; k < b; ++k) g.nucs += (r[k].site_info & 15u) << (4 * (5 - (k - a)));
-        out.push_back(g);
-    };
-    for (int64_t i = 1; i < n; ++i)
-        if (i - start == 6 || pos(i) != pos(i - 1) + 1 || typ(i) != typ(i - 1)) { emit(start, i); start = i; }
-    if (n > 0) emit(start, n);
-}
-
 std::string dump_error(const std::string& e) { return "#error\t" + e + "\n"; }
 
 struct CtxGuard {
@@ -96,23 +65,21 @@ struct MsaResult {
     std::string err;
     Topology t;
     std::string consensus;
-    std::vector<std::vector<Grouped>> muts;   // per node id, NucMut runs in list order
+    PanmanTree tree;   // the topology and every node's NucMut runs; finish_panmat adds the block
 };
 
-// The constructor body: returns the tree, consensus block and per-node NucMut lists.
+// The constructor body: returns the topology, the consensus block and the per-node NucMut lists.
 MsaResult build_result(const char* newick_c, const char* msa_c, const char* ref_c, int mode,
                        const std::vector<int>& devices) {
     MsaResult res;
     PhaseClock clock;
-    std::string newick(newick_c), err;
-    const size_t nl = newick.find('\n');
-    if (nl != std::string::npos) newick.resize(nl);
+    std::string err;
     auto dump_error = [&](const std::string& e) {
         res.err = e;
         return res;
     };
     Topology& t = res.t;
-    if (!parse_topology(newick, t, err)) return dump_error(err);
+    if (!parse_newick(newick_c, t, err)) return dump_error(err);
     const std::string reference = ref_c ? ref_c : "";
 
     std::map<std::string, std::string> rows;
@@ -151,17 +118,12 @@ MsaResult build_result(const char* newick_c, const char* msa_c, const char* ref_
     }
 
     res.consensus = consensus;
-    res.muts.assign(t.name.size(), {});
+    tree_from_topology(t, res.tree, false);   // written or dumped, never handed out: no Newick text
     clock.lap("msa.parse");
     if (width == 0) return res;
 
-    // CSR + leaf rows (rows in name order; leaves missing from the alignment are absent)
+    // leaf rows (rows in name order; leaves missing from the alignment are absent)
     const int32_t N = (int32_t)t.name.size();
-    std::vector<int32_t> off(N + 1, 0), idx;
-    for (int32_t i = 0; i < N; ++i) {
-        idx.insert(idx.end(), t.kids[i].begin(), t.kids[i].end());
-        off[i + 1] = (int32_t)idx.size();
-    }
     std::map<std::string, int32_t> row_of;
     std::vector<const std::string*> row_seq;
     for (auto& r : rows) {
@@ -177,15 +139,17 @@ MsaResult build_result(const char* newick_c, const char* msa_c, const char* ref_
     const int64_t S = (int64_t)width;
     const int64_t stride = (S + 1) / 2;
     std::vector<uint8_t> codes(row_seq.size() * stride, 0);
-    for (size_t r = 0; r < row_seq.size(); ++r)
-        for (int64_t s = 0; s < S; ++s)
-            codes[r * stride + s / 2] |= (uint8_t)(nuc_code((*row_seq[r])[s]) << (4 * (s & 1)));
+    auto pack_row = [S](const std::string& row, uint8_t* out) {
+        const char* text = row.data();
+        pack4_into(out, (size_t)S, [text](size_t s) { return code_of(text[s]); });
+    };
+    for (size_t r = 0; r < row_seq.size(); ++r) pack_row(*row_seq[r], codes.data() + r * stride);
     std::vector<uint8_t> cons4(stride, 0), force4;
-    for (int64_t s = 0; s < S; ++s) cons4[s / 2] |= (uint8_t)(nuc_code(consensus[s]) << (4 * (s & 1)));
+    pack_row(consensus, cons4.data());
     if (ref_row) {
         // M1: refState = 1 << code(ref) (:1419); M2: defaultState = code, gap -> 0 (:1583-1596)
         force4.assign(stride, 0);
-        for (int64_t s = 0; s < S; ++s) force4[s / 2] |= (uint8_t)(nuc_code((*ref_row)[s]) << (4 * (s & 1)));
+        pack_row(*ref_row, force4.data());
     }
 
     // columns split into contiguous even-aligned ranges, one host thread + context per
@@ -222,7 +186,7 @@ MsaResult build_result(const char* newick_c, const char* msa_c, const char* ref_
     };
     const bool uploaded = each([&](int g) {
         const int64_t a = lo[g], ns = lo[g + 1] - lo[g];
-        pm_tree tree{N, t.root, off.data(), idx.data()};
+        const pm_tree tree = tree_view(res.tree);
         if (pm_tree_upload(cg[g].c, &tree) != PM_OK ||
             pm_leaves_upload(cg[g].c, ns, codes.data() + a / 2, stride, node_row.data(), nullptr, 0) != PM_OK ||
             pm_sites_upload(cg[g].c, cons4.data() + a / 2, ref_row ? force4.data() + a / 2 : nullptr) != PM_OK ||
@@ -246,17 +210,10 @@ MsaResult build_result(const char* newick_c, const char* msa_c, const char* ref_
     clock.lap("msa.gpu_run");
     if (uploaded)
         each([&](int g) {
-            int64_t n = 0;
-            if (pm_mutation_count(cg[g].c, &n) != PM_OK) {
+            if (fetch_records(cg[g].c, part[g]) != PM_OK) {
                 msg[g] = pm_last_error(cg[g].c);
                 return;
             }
-            part[g].resize((size_t)std::max<int64_t>(n, 1));
-            if (pm_mutations_fetch(cg[g].c, part[g].data(), n, &n) != PM_OK) {
-                msg[g] = pm_last_error(cg[g].c);
-                return;
-            }
-            part[g].resize((size_t)n);
             for (pm_mut& m : part[g]) m.site_info += (uint32_t)lo[g] << 8;
         });
     for (int g = 0; g < G; ++g)
@@ -274,14 +231,27 @@ MsaResult build_result(const char* newick_c, const char* msa_c, const char* ref_
     if (G > 1) std::stable_sort(recs.begin(), recs.end(), [](const pm_mut& x, const pm_mut& y) { return x.node < y.node; });
     const int64_t n = (int64_t)recs.size();
 
-    for (int64_t a = 0; a < n;) {
-        int64_t b = a;
-        while (b < n && recs[b].node == recs[a].node) ++b;
-        group_node(recs.data() + a, b - a, res.muts[recs[a].node]);
-        a = b;
+    std::vector<Tup> run;   // one node's records: the one block, main positions only
+    for (int64_t a = 0, v = 0; v < N; ++v) {   // the records are in (node, site) order
+        run.clear();
+        for (; a < n && recs[a].node == (uint32_t)v; ++a)
+            run.push_back(Tup{0, (int32_t)(recs[a].site_info >> 8), -1, (uint8_t)((recs[a].site_info >> 4) & 15u),
+                              (uint8_t)(recs[a].site_info & 15u)});
+        append_nuc_muts(res.tree, (int32_t)v, run, {});
     }
     clock.lap("msa.group");
     return res;
+}
+
+// Block(0, consensus) and the root's BlockMut(0, BI, false) around the NucMut lists.
+void finish_panmat(MsaResult& r) {
+    PanmanTree& t = r.tree;
+    t.block_primary.assign(1, 0);
+    t.block_seq = encode_block(r.consensus);
+    t.block_seq_off = {0, (int64_t)t.block_seq.size()};
+    t.gap_off.assign(1, 0);
+    for (int32_t v = 0; v < t.num_nodes; ++v)
+        append_block_muts(t, v, v == t.root ? std::vector<BlockRec>{{0, PM_MUT_NI << 4 | 1}} : std::vector<BlockRec>{});
 }
 
 std::string build(const char* newick_c, const char* msa_c, const char* ref_c, int mode, int device) {
@@ -289,28 +259,18 @@ std::string build(const char* newick_c, const char* msa_c, const char* ref_c, in
     if (!r.err.empty()) return dump_error(r.err);
     std::string dump = "#consensus\t" + r.consensus + "\n";
     dump += "#blockmut\t" + r.t.name[r.t.root] + "\t0\t-1\t1\t0\n";
-    std::map<std::string, const std::vector<Grouped>*> by_name;   // nodes in name order
-    for (size_t v = 0; v < r.muts.size(); ++v)
-        if (!r.muts[v].empty()) by_name[r.t.name[v]] = &r.muts[v];
+    const PanmanTree& t = r.tree;
+    std::map<std::string, int32_t> by_name;   // nodes in name order
+    for (int32_t v = 0; v < t.num_nodes; ++v)
+        if (t.nm_off[v + 1] > t.nm_off[v]) by_name[r.t.name[v]] = v;
     std::ostringstream os;
     for (auto& kv : by_name)
-        for (auto& m : *kv.second) {
+        for (int64_t k = t.nm_off[kv.second]; k < t.nm_off[kv.second + 1]; ++k) {
             char buf[96];
-            std::snprintf(buf, sizeof buf, "\t%d\t-1\t%u\t%06x\n", m.pos, m.info, m.nucs);
+            std::snprintf(buf, sizeof buf, "\t%d\t-1\t%u\t%06x\n", t.nm_pos[k], (unsigned)t.nm_info[k], t.nm_nucs[k]);
             os << kv.first << buf;
         }
     return dump + os.str();
-}
-
-// Block(0, consensus): 8 codes per word, MSB nibble first (src/panman.cpp:246-257).
-std::vector<uint32_t> encode_block(const std::string& seq) {
-    std::vector<uint32_t> w;
-    for (size_t i = 0; i < seq.size(); i += 8) {
-        uint32_t x = 0;
-        for (size_t j = i; j < std::min(i + 8, seq.size()); ++j) x ^= (uint32_t)nuc_code(seq[j]) << (4 * (7 - (j - i)));
-        w.push_back(x);
-    }
-    return w;
 }
 
 }  // namespace
@@ -318,14 +278,21 @@ std::vector<uint32_t> encode_block(const std::string& seq) {
 
 extern "C" {
 
+// (No pm_ctx on these entry points: an allocation failure is answered in their own error channels.)
 char* pm_msa_build(const char* newick, const char* msa_text, const char* reference, int mode, int device) {
-    std::string out;
-    if (!newick || !msa_text || (mode != PM_MODE_FITCH && mode != PM_MODE_SANKOFF)) out = "#error\tbad arguments\n";
-    else out = pm::build(newick, msa_text, reference, mode, device);
-    char* p = static_cast<char*>(std::malloc(out.size() + 1));
-    if (!p) return nullptr;
-    std::memcpy(p, out.data(), out.size() + 1);
-    return p;
+    try {
+        std::string out;
+        if (!newick || !msa_text || (mode != PM_MODE_FITCH && mode != PM_MODE_SANKOFF)) out = "#error\tbad arguments\n";
+        else out = pm::build(newick, msa_text, reference, mode, device);
+        char* p = static_cast<char*>(std::malloc(out.size() + 1));
+        if (p) std::memcpy(p, out.data(), out.size() + 1);
+        return p;
+    } catch (const std::bad_alloc&) {
+        static const char kText[] = "#error\tmsa host buffers\n";
+        char* p = static_cast<char*>(std::malloc(sizeof kText));
+        if (p) std::memcpy(p, kText, sizeof kText);
+        return p;
+    }
 }
 
 void pm_free(void* p) { std::free(p); }
@@ -345,73 +312,25 @@ int pm_msa_to_panman_multi(const char* newick, const char* msa_text, const char*
         set_err("bad arguments");
         return PM_ERR_ARG;
     }
-    pm::MsaResult r = pm::build_result(newick, msa_text, reference, mode,
-                                       std::vector<int>(devices, devices + num_devices));
-    if (!r.err.empty()) {
-        set_err(r.err);
-        return PM_ERR_ARG;
-    }
-    const auto t_conv = std::chrono::steady_clock::now();
-    const int32_t N = (int32_t)r.t.name.size();
-    std::vector<int32_t> off(N + 1, 0), idx;
-    std::string names;
-    for (int32_t i = 0; i < N; ++i) {
-        idx.insert(idx.end(), r.t.kids[i].begin(), r.t.kids[i].end());
-        off[i + 1] = (int32_t)idx.size();
-        names += r.t.name[i];
-        names.push_back('\0');
-    }
-    const std::vector<uint32_t> words = pm::encode_block(r.consensus);
-    const int32_t block_primary = 0;
-    const int64_t seq_off[2] = {0, (int64_t)words.size()};
-    const int64_t gap_off[1] = {0};
-    std::vector<int64_t> bm_off(N + 1, 0), nm_off(N + 1, 0);
-    for (int32_t v = 0; v < N; ++v) bm_off[v + 1] = bm_off[v] + (v == r.t.root ? 1 : 0);
-    const int32_t bm_primary = 0;
-    const uint8_t bm_info = 1, bm_inv = 0;   // root: BlockMut(0, BI, false)
-    std::vector<int32_t> np, ns, npos, ngap;
-    std::vector<uint8_t> ninfo;
-    std::vector<uint32_t> nnucs;
-    for (int32_t v = 0; v < N; ++v) {
-        for (auto& m : r.muts.empty() ? std::vector<pm::Grouped>() : r.muts[v]) {
-            np.push_back(0);
-            ns.push_back(-1);
-            npos.push_back(m.pos);
-            ngap.push_back(-1);
-            ninfo.push_back((uint8_t)m.info);
-            nnucs.push_back(m.nucs);
+    try {
+        pm::MsaResult r = pm::build_result(newick, msa_text, reference, mode, std::vector<int>(devices, devices + num_devices));
+        if (!r.err.empty()) {
+            set_err(r.err);
+            return PM_ERR_ARG;
         }
-        nm_off[v + 1] = (int64_t)np.size();
+        const auto t_conv = std::chrono::steady_clock::now();
+        pm::finish_panmat(r);
+        pm_panmat p{};
+        r.tree.view(p);
+        const pm_panmat* list[1] = {&p};
+        pm::phase_add("msa.to_panmat", pm::seconds_since(t_conv));
+        const int rc = pm_panman_write(out_path, list, 1, 1);
+        if (rc != PM_OK) set_err(std::string("cannot write ") + out_path);
+        return rc;
+    } catch (const std::bad_alloc&) {
+        set_err("msa host buffers");
+        return PM_ERR_OOM;
     }
-    pm_panmat p{};
-    p.num_nodes = N;
-    p.root = r.t.root;
-    p.child_offsets = off.data();
-    p.child_index = idx.data();
-    p.names = names.data();
-    p.num_blocks = 1;
-    p.block_primary = &block_primary;
-    p.block_seq_offsets = seq_off;
-    p.block_seq = words.data();
-    p.num_gaps = 0;
-    p.gap_offsets = gap_off;
-    p.block_mut_offsets = bm_off.data();
-    p.block_mut_primary = &bm_primary;
-    p.block_mut_info = &bm_info;
-    p.block_mut_inversion = &bm_inv;
-    p.nuc_mut_offsets = nm_off.data();
-    p.nuc_mut_primary = np.data();
-    p.nuc_mut_secondary = ns.data();
-    p.nuc_mut_position = npos.data();
-    p.nuc_mut_gap_position = ngap.data();
-    p.nuc_mut_info = ninfo.data();
-    p.nuc_mut_nucs = nnucs.data();
-    p.branch_length = r.t.length.data();
-    const pm_panmat* list[1] = {&p};
-    pm::phase_add("msa.to_panmat", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_conv).count());
-    const int rc = pm_panman_write(out_path, list, 1, 1);
-    if (rc != PM_OK) set_err(std::string("cannot write ") + out_path);
-    return rc;
 }
 
 }  // extern "C"

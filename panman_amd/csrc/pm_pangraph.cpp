@@ -23,11 +23,10 @@
 #include <utility>
 #include <vector>
 
+#include "pm_build.h"
 #include "pm_chain.h"
-#include "pm_internal.h"
+#include "pm_dev.h"
 #include "pm_json.h"
-#include "pm_newick.h"
-#include "pm_panman_tree.h"
 
 namespace pm {
 namespace {
@@ -260,65 +259,14 @@ struct Column {   // one nucleotide column of the PanMAT
 
 using Seq = std::vector<std::pair<char, std::vector<char>>>;
 
-int fetch_records(pm_ctx* c, std::vector<pm_mut>& recs) {
-    int64_t n = 0;
-    int rc = pm_mutation_count(c, &n);
-    if (rc != PM_OK) return rc;
-    recs.resize((size_t)n);
-    return n ? pm_mutations_fetch(c, recs.data(), n, &n) : PM_OK;
-}
-
-std::vector<uint8_t> pack4(const std::vector<uint8_t>& codes) {
-    std::vector<uint8_t> out((codes.size() + 1) / 2, 0);
-    for (size_t s = 0; s < codes.size(); ++s) out[s / 2] |= (uint8_t)(codes[s] << (4 * (s & 1)));
-    return out;
-}
-
-struct Tup {
-    int32_t block, pos, gap;
-    uint8_t type, code;
-};
-
-// NucMut runs (src/panman.cpp:1236-1272): same rules as the reroot driver.
-void group(std::vector<Tup>& v, bool gap, PanmanTree& out) {
-    std::sort(v.begin(), v.end(), [](const Tup& a, const Tup& b) {
-        return std::tie(a.block, a.pos, a.gap) < std::tie(b.block, b.pos, b.gap);
-    });
-    size_t start = 0;
-    auto emit = [&](size_t a, size_t b) {
-        uint32_t nucs = 0;
-        for (size_t i = a; i < b; ++i) nucs |= (uint32_t)v[i].code << (4 * (5 - (i - a)));
-        out.nm_primary.push_back(v[a].block);
-        out.nm_secondary.push_back(-1);
-        out.nm_pos.push_back(v[a].pos);
-        out.nm_gap.push_back(gap ? v[a].gap : -1);
-        out.nm_info.push_back((uint8_t)(((b - a) << 4) + v[a].type));
-        out.nm_nucs.push_back(nucs);
-    };
-    for (size_t i = 1; i < v.size(); ++i) {
-        const Tup& p = v[i - 1];
-        const Tup& q = v[i];
-        const bool brk = i - start == 6 || q.block != p.block || q.type != p.type ||
-                         (gap ? (q.pos != p.pos || q.gap != p.gap + 1) : q.pos != p.pos + 1);
-        if (brk) {
-            emit(start, i);
-            start = i;
-        }
-    }
-    if (!v.empty()) emit(start, v.size());
-}
-
 int build(pm_ctx* c, const char* json_text, const char* newick_c, const char* ref_c, PanmanTree& out) {
     std::string err;
     Json doc;
     if (!json_parse(json_text, doc, err)) return fail(c, PM_ERR_ARG, "PanGraph JSON: " + err);
     Pangraph pg;
     if (!load_pangraph(doc, pg, err)) return fail(c, PM_ERR_ARG, err);
-    std::string newick(newick_c);
-    const size_t nl = newick.find('\n');
-    if (nl != std::string::npos) newick.resize(nl);
     Topology t;
-    if (!parse_topology(newick, t, err)) return fail(c, PM_ERR_ARG, "Newick: " + err);
+    if (!parse_newick(newick_c, t, err)) return fail(c, PM_ERR_ARG, "Newick: " + err);
     const std::string reference = ref_c ? ref_c : "";
     const int32_t N = (int32_t)t.name.size();
     bool polytomy = false;
@@ -384,21 +332,13 @@ int build(pm_ctx* c, const char* json_text, const char* newick_c, const char* re
             }
     }
 
-    pm_tree tree{};
-    std::vector<int32_t> off(N + 1, 0), idx;
-    for (int32_t v = 0; v < N; ++v) {
-        idx.insert(idx.end(), t.kids[v].begin(), t.kids[v].end());
-        off[v + 1] = (int32_t)idx.size();
-    }
-    tree.num_nodes = N;
-    tree.root = t.root;
-    tree.child_offsets = off.data();
-    tree.child_index = idx.data();
+    tree_from_topology(t, out);
+    const pm_tree tree = tree_view(out);
     int rc = pm_tree_upload(c, &tree);
     if (rc != PM_OK) return rc;
 
     // ---- block mutations (:870-982): one column per block, every aligned sequence present
-    std::vector<std::vector<std::pair<int32_t, uint8_t>>> bmuts(N);
+    std::vector<std::vector<BlockRec>> bmuts(N);
     {
         const int64_t stride = ((int64_t)T + 1) / 2;
         std::vector<uint8_t> codes((size_t)std::max(R, 1) * std::max<int64_t>(stride, 1), 0);
@@ -446,9 +386,8 @@ int build(pm_ctx* c, const char* json_text, const char* newick_c, const char* re
             std::vector<uint8_t> cons_p = pack4(std::vector<uint8_t>(cs.size(), 0)), forced_p = pack4(fc);
             std::vector<pm_mut> recs;
             if ((rc = pm_leaves_upload(c, S, sub.data(), st, node_row.data(), nullptr, 0)) != PM_OK ||
-                (rc = pm_sites_upload(c, cons_p.data(), f ? forced_p.data() : nullptr)) != PM_OK ||
-                (rc = pm_run(c, polytomy ? PM_MODE_BLOCK_SANKOFF : PM_MODE_BLOCK_FITCH)) != PM_OK ||
-                (rc = fetch_records(c, recs)) != PM_OK)
+                (rc = run_columns(c, polytomy ? PM_MODE_BLOCK_SANKOFF : PM_MODE_BLOCK_FITCH, cons_p, f ? forced_p.data() : nullptr,
+                                  recs)) != PM_OK)
                 return rc;
             for (const pm_mut& m : recs)
                 bmuts[m.node].emplace_back((int32_t)cs[m.site_info >> 8], (uint8_t)(m.site_info & 0xFF));
@@ -582,8 +521,7 @@ int build(pm_ctx* c, const char* json_text, const char* newick_c, const char* re
             const std::vector<uint8_t> cons_p = pack4(cons_c), forced_p = pack4(forced_c);
             std::vector<pm_mut> recs;
             if ((rc = pm_leaves_upload(c, S, codes.data(), st, node_row.data(), pres.data(), pst)) != PM_OK ||
-                (rc = pm_sites_upload(c, cons_p.data(), f ? forced_p.data() : nullptr)) != PM_OK ||
-                (rc = pm_run(c, mode)) != PM_OK || (rc = fetch_records(c, recs)) != PM_OK)
+                (rc = run_columns(c, mode, cons_p, f ? forced_p.data() : nullptr, recs)) != PM_OK)
                 return rc;
             for (const pm_mut& m : recs) {
                 const Column& col = columns[cs[c0 + (m.site_info >> 8)]];
@@ -594,17 +532,6 @@ int build(pm_ctx* c, const char* json_text, const char* newick_c, const char* re
     }
 
     // ---- the PanMAT
-    out.num_nodes = N;
-    out.root = t.root;
-    out.child_off = off;
-    out.child_idx = idx;
-    out.names_blob.clear();
-    for (int32_t v = 0; v < N; ++v) {
-        out.names_blob += t.name[v];
-        out.names_blob.push_back('\0');
-    }
-    out.length = t.length;
-    out.newick = newick_of(t);
     out.block_seq_off.assign(1, 0);
     out.gap_off.assign(1, 0);
     for (size_t i = 0; i < T; ++i) {
@@ -620,25 +547,14 @@ int build(pm_ctx* c, const char* json_text, const char* newick_c, const char* re
         }
         out.gap_off.push_back((int64_t)out.gap_pos.size());
     }
-    out.bm_off.assign(N + 1, 0);
-    out.nm_off.assign(N + 1, 0);
+    const auto by_site = [](const Tup& a, const Tup& b) { return std::tie(a.block, a.pos, a.gap) < std::tie(b.block, b.pos, b.gap); };
     for (int32_t v = 0; v < N; ++v) {
-        auto& bl = bmuts[v];
-        std::sort(bl.begin(), bl.end());   // block order (the reference's is TBB-scheduled)
-        for (auto& bm : bl) {
-            const int type = bm.second >> 4, code = bm.second & 15;
-            out.bm_primary.push_back(bm.first);
-            out.bm_info.push_back(type == PM_MUT_NI ? 1 : 0);
-            out.bm_inv.push_back(type == PM_MUT_NI ? code == 2 : type == PM_MUT_NS);
-        }
-        out.bm_off[v + 1] = (int64_t)out.bm_primary.size();
-        group(main_t[v], false, out);
-        group(gap_t[v], true, out);
-        out.nm_off[v + 1] = (int64_t)out.nm_primary.size();
+        std::sort(bmuts[v].begin(), bmuts[v].end());   // block order (the reference's is TBB-scheduled)
+        append_block_muts(out, v, bmuts[v]);
+        std::sort(main_t[v].begin(), main_t[v].end(), by_site);   // the two runs' records arrive apart
+        std::sort(gap_t[v].begin(), gap_t[v].end(), by_site);
+        append_nuc_muts(out, v, main_t[v], gap_t[v]);
     }
-    out.circular.assign(N, -1);
-    out.rotation.assign(N, 0);
-    out.inverted.assign(N, 0);
     for (int32_t v = 0; v < N; ++v) {
         auto a = pg.circular.find(t.name[v]);
         if (a != pg.circular.end()) out.circular[v] = a->second;
@@ -655,15 +571,5 @@ int build(pm_ctx* c, const char* json_text, const char* newick_c, const char* re
 
 extern "C" int pm_pangraph_build(pm_ctx* c, const char* json, const char* newick, const char* reference, pm_panman** out) {
     if (!c || !json || !newick || !out) return PM_ERR_ARG;
-    *out = nullptr;
-    (void)hipSetDevice(c->device);
-    auto* res = new pm_panman();
-    res->trees.resize(1);
-    const int rc = pm::build(c, json, newick, reference, res->trees[0]);
-    if (rc != PM_OK) {
-        delete res;
-        return rc;
-    }
-    *out = res;
-    return PM_OK;
+    return pm::build_handle(c, "pangraph", out, [&](pm::PanmanTree& tree) { return pm::build(c, json, newick, reference, tree); });
 }

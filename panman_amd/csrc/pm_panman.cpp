@@ -35,9 +35,8 @@
 #include <utility>
 #include <vector>
 
+#include "pm_build.h"
 #include "pm_internal.h"
-#include "pm_newick.h"
-#include "pm_panman_tree.h"
 
 // ---- liblzma (linked as liblzma.so.5; prototypes of its stable C ABI) ----------------
 extern "C" {
@@ -524,20 +523,9 @@ bool load_tree(Msg& m, const Struct& t, PanmanTree& out) {
     std::string err;
     if (!parse_topology(out.newick, topo, err)) return m.fail("newick: " + err);
     const int32_t N = (int32_t)topo.name.size();
-    out.num_nodes = N;
-    out.root = topo.root;
-    out.length = topo.length;
-    out.child_off.assign(N + 1, 0);
-    for (int32_t i = 0; i < N; ++i) {
-        out.child_idx.insert(out.child_idx.end(), topo.kids[i].begin(), topo.kids[i].end());
-        out.child_off[i + 1] = (int32_t)out.child_idx.size();
-    }
+    set_topology(topo, out);
     std::unordered_map<std::string, int32_t> index;
-    for (int32_t i = 0; i < N; ++i) {
-        out.names_blob += topo.name[i];
-        out.names_blob.push_back('\0');
-        index[topo.name[i]] = i;
-    }
+    for (int32_t i = 0; i < N; ++i) index[topo.name[i]] = i;
     // nodes: assignMutationsToNodes walks the tree in pre-order (src/panman.cpp:576-618).  Two
     // passes over node ranges on host threads: each node's mutation counts, then -- at offsets
     // from their prefix sums -- the flattened mutations (the message is only read: no state)
@@ -820,20 +808,9 @@ bool load_tree_pb(const uint8_t* b, const uint8_t* e, PanmanTree& out, std::stri
     Topology topo;
     if (!parse_topology(out.newick, topo, err)) { err = "newick: " + err; return false; }
     const int32_t N = (int32_t)topo.name.size();
-    out.num_nodes = N;
-    out.root = topo.root;
-    out.length = topo.length;
-    out.child_off.assign(N + 1, 0);
-    for (int32_t i = 0; i < N; ++i) {
-        out.child_idx.insert(out.child_idx.end(), topo.kids[i].begin(), topo.kids[i].end());
-        out.child_off[i + 1] = (int32_t)out.child_idx.size();
-    }
+    set_topology(topo, out);
     std::unordered_map<std::string, int32_t> index;
-    for (int32_t i = 0; i < N; ++i) {
-        out.names_blob += topo.name[i];
-        out.names_blob.push_back('\0');
-        index[topo.name[i]] = i;
-    }
+    for (int32_t i = 0; i < N; ++i) index[topo.name[i]] = i;
     // nodes: i-th stored node = i-th node in pre-order (assignMutationsToNodes)
     out.bm_off.assign(N + 1, 0);
     out.nm_off.assign(N + 1, 0);

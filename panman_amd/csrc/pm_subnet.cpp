@@ -17,9 +17,8 @@
 #include <unordered_map>
 #include <vector>
 
+#include "pm_build.h"
 #include "pm_dev.h"
-#include "pm_newick.h"
-#include "pm_panman_tree.h"
 
 namespace pm {
 namespace {
@@ -336,39 +335,30 @@ int subnet(pm_ctx* c, const pm_panmat* p, const char* const* ids, int64_t num_id
     Topology topo;
     topo.root = 0;
     topo.kids.resize(M);
-    out.num_nodes = M;
-    out.root = 0;
-    out.child_off.assign(M + 1, 0);
     for (int32_t v = 1; v < M; ++v) topo.kids[t.parent[v]].push_back(v);   // (ascending: the original order)
-    out.circular.assign(M, -1);
-    out.rotation.assign(M, 0);
-    out.inverted.assign(M, 0);
     for (int32_t v = 0; v < M; ++v) {
         const int32_t* ch = t.chain.data() + t.chain_off[v];
-        const int32_t links = t.chain_off[v + 1] - t.chain_off[v], bottom = ch[links - 1];
-        topo.name.push_back(name[bottom]);
-        out.names_blob += name[bottom];
-        out.names_blob.push_back('\0');
+        const int32_t links = t.chain_off[v + 1] - t.chain_off[v];
+        topo.name.push_back(name[ch[links - 1]]);
         if (p->branch_length) {
             float len = p->branch_length[ch[0]];
             for (int32_t l = 1; l < links; ++l) len += p->branch_length[ch[l]];   // par->branchLength += chi->branchLength
             topo.length.push_back(len);
         }
-        for (int32_t k : topo.kids[v]) out.child_idx.push_back(k);
-        out.child_off[v + 1] = (int32_t)out.child_idx.size();
+    }
+    tree_from_topology(topo, out);
+    for (int32_t v = 0; v < M; ++v) {
         // kept by the surviving name; the reference also keeps the entries of dropped names, which nothing reads
+        const int32_t bottom = t.chain[t.chain_off[v + 1] - 1];
         if (p->circular_offset) out.circular[v] = p->circular_offset[bottom];
         if (p->rotation_index) out.rotation[v] = p->rotation_index[bottom];
         if (p->sequence_inverted) out.inverted[v] = p->sequence_inverted[bottom];
     }
-    out.length = topo.length;
-    out.newick = newick_of(topo);
 
     // 2. block mutations, and the merged chains' nucleotide records in chain order
     Records rec;
     std::vector<int64_t> node_rec{0}, node_bases{0};   // per merged node: prefix of its records and bases
     std::vector<int32_t> merged;
-    out.bm_off.assign(M + 1, 0);
     for (int32_t v = 0; v < M; ++v) {
         const int32_t* ch = t.chain.data() + t.chain_off[v];
         const int32_t links = t.chain_off[v + 1] - t.chain_off[v];
@@ -459,14 +449,7 @@ int subnet(pm_ctx* c, const pm_panmat* p, const char* const* ids, int64_t num_id
     }
 
     // 4. the new tree's arrays
-    out.block_primary.assign(p->block_primary, p->block_primary + p->num_blocks);
-    out.block_seq_off.assign(p->block_seq_offsets, p->block_seq_offsets + p->num_blocks + 1);
-    out.block_seq.assign(p->block_seq, p->block_seq + p->block_seq_offsets[p->num_blocks]);
-    out.gap_primary.assign(p->gap_primary, p->gap_primary + p->num_gaps);
-    out.gap_off.assign(p->gap_offsets, p->gap_offsets + p->num_gaps + 1);
-    out.gap_pos.assign(p->gap_position, p->gap_position + p->gap_offsets[p->num_gaps]);
-    out.gap_len.assign(p->gap_length, p->gap_length + p->gap_offsets[p->num_gaps]);
-    out.nm_off.assign(M + 1, 0);
+    copy_blocks(*p, out);
     int64_t at = 0;   // cursor in the packed records (new-node order, as the batches ran)
     for (int32_t v = 0; v < M; ++v) {
         if (t.chain_off[v + 1] - t.chain_off[v] == 1) {
@@ -501,18 +484,5 @@ int subnet(pm_ctx* c, const pm_panmat* p, const char* const* ids, int64_t num_id
 
 extern "C" int pm_subnet(pm_ctx* c, const pm_panmat* p, const char* const* ids, int64_t num_ids, pm_panman** out) {
     if (!c || !p || !out || (!ids && num_ids > 0)) return PM_ERR_ARG;
-    *out = nullptr;
-    (void)hipSetDevice(c->device);
-    auto* res = new (std::nothrow) pm_panman();
-    if (!res) return pm::fail(c, PM_ERR_OOM, "subnet host buffers");
-    const int rc = pm::guarded(c, "subnet", [&]() {
-        res->trees.resize(1);
-        return pm::subnet(c, p, ids, num_ids, res->trees[0]);
-    });
-    if (rc != PM_OK) {
-        delete res;
-        return rc;
-    }
-    *out = res;
-    return PM_OK;
+    return pm::build_handle(c, "subnet", out, [&](pm::PanmanTree& tree) { return pm::subnet(c, p, ids, num_ids, tree); });
 }
