@@ -167,6 +167,9 @@ int pm_set_stream(pm_ctx* ctx, void* hip_stream);
  *   PM_OPT_SUBNET_BATCH_ENTRIES (default 2^25, 1 .. 2^31 - 2): pm_subnet expands, sorts and folds the merged
  *                  chains' nucleotide mutations in batches of whole new nodes of at most this many bases (a node
  *                  whose chain holds more gets a batch of its own).  The result does not depend on it.
+ *   PM_OPT_AA_BATCH_BYTES (default 1 GiB, at least 4096): pm_aa / pm_aa_fd build the codon tables and
+ *                  the lines of a batch of nodes in at most this much device memory (always at least
+ *                  one node) and stream the text batch by batch.  The text does not depend on it.
  * (Option ids 1, 4, 5 and 11 -- subtree-region, heavy-path-chain and level-band schedules,
  * tail records overlapped with the pre-order levels -- were measured slower than, or no
  * faster than, the level kernels on MI355X and removed.) */
@@ -189,6 +192,7 @@ int pm_set_stream(pm_ctx* ctx, void* hip_stream);
 #define PM_OPT_DOWN_PACK 22
 #define PM_OPT_GFA_IN_BATCH_SITES 23
 #define PM_OPT_SUBNET_BATCH_ENTRIES 24
+#define PM_OPT_AA_BATCH_BYTES 25
 int pm_set_option(pm_ctx* ctx, int option, int64_t value);
 /* Accumulate per-kernel-class device time with HIP events (see pm_kernel_times). */
 int pm_set_profiling(pm_ctx* ctx, int enable);
@@ -534,6 +538,65 @@ int pm_maf_fd(pm_ctx* ctx, const pm_panmat* panmat, int fd, int64_t* length);
  * PM_ERR_UNSUPPORTED; a failed write: PM_ERR_ARG (errno kept), as pm_fasta_fd. */
 int pm_gfa(pm_ctx* ctx, const pm_panmat* panmat, char** text, int64_t* length);
 int pm_gfa_fd(pm_ctx* ctx, const pm_panmat* panmat, int fd, int64_t* length);
+/* Drop-in for Tree::extractAminoAcidTranslations(fout, start, end) (src/aaTrans.cpp:185-304; the
+ * --aa-translation command, src/panmanUtils.cpp:895-938): per node of the tree, internal ones
+ * included, the amino-acid substitutions, insertions and deletions of the window between two
+ * global coordinates against the root's.  Rotation, sequence inversion and circular offset play
+ * no part (getSequenceFromReference(rotate = false)); a node's sequence is its canonical row:
+ * per held block, per position 0..n_b (n_b the 'x' sentinel) its gap slots, then its main
+ * character.  An absent block counts as forward.
+ *   locate(v, g)  globalCoordinateToBlockCoordinate with circular offset 0 (src/panman.cpp:
+ *                 5726-5798): L = the characters of v's held blocks that are neither '-' nor 'x';
+ *                 g' = g when g < L, else g - L (one wrap: a negative or still too large g' is not
+ *                 found); held blocks in ascending id, a forward block's positions ascending (slots
+ *                 ascending, then the main character), a reverse block's descending (the main
+ *                 character, then slots descending); the g'-th such character is (b, j, k), k = -1
+ *                 for a main character.
+ *   window(v, S = (b0, j0, k0), E)  getNucleotideSequenceFromBlockCoordinates (aaTrans.cpp:3-67),
+ *                 quirks included.  For every id b0..b1 (an id without a block has no position; a
+ *                 block that is not held emits '-' per character): a forward block walks j from
+ *                 (i == b0 ? j0 : 0) up to n_i, in every position the slots k0.. when k0 >= 0 and no
+ *                 slot at all when k0 == -1 (the reference's slot loop always starts at
+ *                 get<3>(start)), then the main character; a reverse block walks j from
+ *                 (i == b0 ? j0 : n_0) down to 0 -- n_0 being block id 0's last index, as the
+ *                 reference reads sequence[0] -- the main character first, then the slots from
+ *                 (i == b0 and j == j0 ? k0 : the last) down to 0.  Before every character the
+ *                 walk stops if its coordinate is E; a walk that never stops is "ERROR".
+ *   codons(W)     every character that is not A, C, G or T becomes '-'; the others are grouped in
+ *                 threes in order, codon c = (amino acid of the standard genetic code as its
+ *                 three-letter name, "*" for TAA, TAG and TGA; the window index of its first and
+ *                 of its third character); an incomplete last group is dropped; "ERROR": none.
+ * The call: every node, the root included, is located and windowed on its own row; a node whose S
+ * or E is not found is counted in `*unlocated` and prints no line.  Every node's codons are merged
+ * against the root's (aa, start, end) lists with the reference's two-pointer loop
+ * (aaTrans.cpp:259-285); a node whose window is "ERROR" has no codons, so every root codon is a
+ * deletion.  A node's string: "S:<root index>:<AA>;" per match whose amino acid differs, then
+ * "I:<root index>:<AA>;" per insertion, then "D:<root index>;" per deletion.
+ * Text: "node_id\taa_mutations\n", then "<name>\t<string>\n" per node with a non-empty string.
+ * `*ref_codons` = the root's codon count (the reference prints it three times on stdout); when it
+ * is 0 the text is empty and the call returns PM_OK, as the reference returns before its header.
+ * Deviations: lines are in node-id order (the reference iterates a tbb::concurrent_unordered_map);
+ * a root window that is "ERROR" returns PM_ERR_ARG (the reference goes on and reports every node's
+ * codons as insertions at 0); a reverse-strand block i != b0 inside some located node's window
+ * with n_0 > n_i, or without a block of id 0, returns PM_ERR_UNSUPPORTED (the reference indexes
+ * out of range there).
+ * The rows of all nodes come from one replay of a derived PanMAT in which every internal node has
+ * one more childless child without mutations (that child's row is the node's), so the replay
+ * kernels are pm_fasta's.  Per-block sizes, the rank-select of both coordinates, the codon tables,
+ * the merge (an order-free form of the two-pointer loop, one codon per lane), the line lengths and
+ * the text are computed on the GPU (profiling class 3), batch by batch of nodes
+ * (PM_OPT_AA_BATCH_BYTES), the text streamed through the pinned download slots.  Phase log: aa.*.
+ * Memory: the replayed rows are nodes x columns bytes, as leaves x columns for the other
+ * extractions; sharding by node ranges and a window-only replay are not implemented.
+ * `*text` is malloc'd (release with pm_free); pm_aa_fd writes to `fd` instead (`length`,
+ * `ref_codons`, `unlocated` nullable).  Errors: end <= start: PM_ERR_ARG ("End coordinate must be
+ * greater than start"); the root's S or E not found: PM_ERR_ARG ("coordinates out of range"); a
+ * nucleotide mutation on a secondary block: PM_ERR_UNSUPPORTED (as pm_maf); rows of 2^31 columns
+ * or more: PM_ERR_UNSUPPORTED; a failed write: PM_ERR_ARG (errno kept), as pm_fasta_fd. */
+int pm_aa(pm_ctx* ctx, const pm_panmat* panmat, int64_t start, int64_t end, char** text, int64_t* length,
+          int64_t* ref_codons, int64_t* unlocated);
+int pm_aa_fd(pm_ctx* ctx, const pm_panmat* panmat, int64_t start, int64_t end, int fd, int64_t* length,
+             int64_t* ref_codons, int64_t* unlocated);
 /* Canonical aligned columns per leaf of the prepared PanMAT (gap slots before each main
  * position, block sentinels included) and the number of leaves. */
 int pm_replay_shape(pm_ctx* ctx, int64_t* leaves, int64_t* columns, int64_t* edits);

@@ -163,6 +163,20 @@ class Tree {
         pm_free(text);
     }
 
+    // Tree::extractAminoAcidTranslations(fout, start, end) (src/aaTrans.cpp:185-304); the lines in
+    // node-id order, the root's codon count on std::cout as the reference prints it.  An error the
+    // reference only prints (end <= start, coordinates out of range) throws.
+    void extractAminoAcidTranslations(std::ostream& fout, int64_t start, int64_t end) const {
+        detail::Ctx ctx(device_);
+        pm_panmat v = view();
+        char* text = nullptr;
+        int64_t len = 0, codons = 0;
+        ctx.check(pm_aa(ctx.c, &v, start, end, &text, &len, &codons, nullptr), "pm_aa");
+        std::cout << codons << " " << codons << " " << codons << std::endl;
+        fout.write(text, (std::streamsize)len);
+        pm_free(text);
+    }
+
     // Tree::printSummary(out) (src/summary.cpp:257-273); the block lines go to std::cout as
     // getBlockMutationsParallel prints them (:203-250).
     void printSummary(std::ostream& out) const {

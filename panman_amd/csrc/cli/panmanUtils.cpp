@@ -1,6 +1,7 @@
 // panmanUtils-compatible command line for the GPU path (src/panmanUtils.cpp:128-182 option
 // table, :1302-1325 PanMAN load, :1409-1465 MSA build, :1326-1362 GFA build, :271-299 writePanMAN, :385-415 and
-// :458-490 FASTA / aligned FASTA, :584-652 subnetwork extraction, :699-732 GFA, :741-763 MAF, :766-786 Newick).  Only the commands on the accelerated
+// :458-490 FASTA / aligned FASTA, :584-652 subnetwork extraction, :699-732 GFA, :741-763 MAF, :766-786 Newick,
+// :895-938 amino-acid translation).  Only the commands on the accelerated
 // path are implemented; any other reference command is rejected with a message.
 #include <fcntl.h>
 #include <unistd.h>
@@ -57,7 +58,10 @@ const Spec kSpecs[] = {
     {"subnet", 'b', false, "Extract subnet of given PanMAN to a new PanMAN file based on the list of nodes provided in the input-file"},
     {"input-file", 'i', true, "Path to the input file, required for --subnet (one line per tree: treeID id id ...)"},
     {"reroot", 'r', false, "Reroot a PanMAT in a PanMAN based on the input sequence id (--reference)"},
-    {"treeID", 'd', true, "Tree ID, required for --reroot; the tree of --maf and --gfa (default 0)"},
+    {"aa-translation", 0, false, "Extract amino acid translations in TSV file (needs --treeID, --start and --end)"},
+    {"start", 'x', true, "Start coordinate of protein translation"},
+    {"end", 'y', true, "End coordinate of protein translation"},
+    {"treeID", 'd', true, "Tree ID, required for --reroot and --aa-translation; the tree of --maf and --gfa (default 0)"},
     {"protobuf2capnp", 0, false, "Converts a Google Protobuf PanMAN (-I) to a Cap'n Proto PanMAN (-o)"},
     {"low-mem-mode", 0, false, "Build with the Sankoff driver (the reference's batched low-memory mode)"},
     {"reference", 'n', true, "Identifier of reference sequence for PanMAN construction (optional) or reroot (required)"},
@@ -71,7 +75,7 @@ const Spec kSpecs[] = {
 // Reference commands outside the accelerated path: recognised so the error is explicit.
 const char* const kOther[] = {"impute", "create-network", "printTips",
                               "vcf", "annotate",
-                              "aa-translation", "extended-newick", "printMutations", "acr", "index",
+                              "extended-newick", "printMutations", "acr", "index",
                               "toUsher"};
 
 void usage(std::ostream& os) {
@@ -384,6 +388,70 @@ int one_tree_text(const Options& o, const pm_panman* file, int device, const cha
     return status;
 }
 
+// -I in.panman --aa-translation --treeID k -x start -y end [-o out] (src/panmanUtils.cpp:895-938):
+// Tree::extractAminoAcidTranslations of one tree to stdout or ./info/<out>.tsv (pm_aa / pm_aa_fd).
+// stdout receives the reference's "<n> <n> <n>" line (the sizes of the root's three codon lists)
+// before the text and the timing line after it.
+int aa_translation(const Options& o, const pm_panman* file, int device) {
+    if (!o.has("treeID")) {
+        print_error("TreeID not provided!");
+        usage(std::cout);
+        return 1;
+    }
+    const int tree_id = std::atoi(o.get("treeID").c_str());
+    if (tree_id < 0 || tree_id >= pm_panman_tree_count(file)) {
+        print_error("TreeID out of range");
+        return 1;
+    }
+    if (!o.has("start") || !o.has("end")) {
+        std::cout << "Start/End Coordinate not provided" << std::endl;
+        return 1;
+    }
+    const int64_t start = std::strtoll(o.get("start").c_str(), nullptr, 10), end = std::strtoll(o.get("end").c_str(), nullptr, 10);
+    pm_ctx* ctx = nullptr;
+    if (pm_create(device, &ctx) != PM_OK) {
+        print_error("no HIP device");
+        return 1;
+    }
+    int fd = -1;
+    const bool to_file = o.has("output-file");
+    if (to_file) {
+        const std::string p = "./info/" + o.get("output-file") + ".tsv";
+        fd = ::open(p.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (fd < 0) {
+            print_error("cannot write " + p);
+            pm_destroy(ctx);
+            return 1;
+        }
+    }
+    int status = 0;
+    pm_panmat view;
+    char* text = nullptr;
+    int64_t len = 0, codons = 0, unlocated = 0;
+    const auto t0 = Clock::now();
+    int rc = pm_panman_tree(file, tree_id, &view);
+    if (rc == PM_OK)
+        rc = to_file ? pm_aa_fd(ctx, &view, start, end, fd, &len, &codons, &unlocated)
+                     : pm_aa(ctx, &view, start, end, &text, &len, &codons, &unlocated);
+    if (rc != PM_OK) {
+        print_error(pm_last_error(ctx));
+        status = 1;
+    } else {
+        std::cout << codons << " " << codons << " " << codons << std::endl;
+        if (!to_file) {
+            std::cout.flush();
+            if (std::fwrite(text, 1, (size_t)len, stdout) != (size_t)len || std::fflush(stdout) != 0) status = 1;
+        }
+        if (unlocated) std::cerr << unlocated << " nodes: coordinates out of range, no line\n";
+    }
+    const long long t = ns_since(t0);
+    pm_free(text);
+    if (to_file && ::close(fd) != 0) status = 1;
+    pm_destroy(ctx);
+    if (status == 0) std::cout << "\nAmino Acid translate execution time: " << t << " nanoseconds\n";
+    return status;
+}
+
 // -P pangraph.json -N tree.nwk -o out [-n ref] (src/panmanUtils.cpp:1364-1407)
 int build_from_pangraph(const Options& o, int device) {
     if (!o.has("input-newick")) {
@@ -569,6 +637,11 @@ int from_panman(const Options& o, const std::vector<int>& devices) {
     }
     if (o.has("gfa")) {
         status = one_tree_text(o, file, device, ".gfa", pm_gfa_fd, "GFA generation time: ");
+        pm_panman_free(file);
+        return status;
+    }
+    if (o.has("aa-translation")) {
+        status = aa_translation(o, file, device);
         pm_panman_free(file);
         return status;
     }

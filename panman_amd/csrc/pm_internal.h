@@ -401,6 +401,7 @@ struct pm_ctx {
     int64_t maf_batch_bytes = (int64_t)1 << 30;   // pm_maf: text per device batch of whole lines (PM_OPT_MAF_BATCH_BYTES)
     int64_t gfa_batch_bytes = (int64_t)1 << 30;   // pm_gfa: text per device batch of whole P lines (PM_OPT_GFA_BATCH_BYTES)
     int64_t gfa_in_batch_sites = pm::kMaxUploadSites; // pm_gfa_build: block columns per upload and run (PM_OPT_GFA_IN_BATCH_SITES)
+    int64_t aa_batch_bytes = (int64_t)1 << 30;    // pm_aa: codon tables and text per device batch of nodes (PM_OPT_AA_BATCH_BYTES)
     int64_t subnet_batch_entries = pm::kSubnetBatchEntries;   // pm_subnet: expanded bases sorted per batch (PM_OPT_SUBNET_BATCH_ENTRIES)
 };
 
@@ -803,6 +804,56 @@ struct SubnetOut {
 };
 hipError_t launch_subnet_pack(pm_ctx* c, const SubnetLive& s, const SubnetOut& o);
 hipError_t warm_subnet();
+// Amino-acid translation (pm_aa.hip; Tree::extractAminoAcidTranslations, src/aaTrans.cpp:185-304)
+// over the replayed rows of every node: node v's row is rows[row_of[v]].  A cell of the canonical
+// row is a column; col_main / col_first give the column of its position's main character and of the
+// position's first gap slot, so its slot index is column - col_first (-1 at col_main).
+constexpr int32_t kAaChunk = 256;        // window cells per round of k_aa_codons' workgroup
+struct AaSpan {
+    int32_t cs, ce;                // the columns of locate(start) and locate(end); -1: not found
+    int32_t b0, b1;                // their blocks
+};
+struct AaArgs {
+    const char* rows;
+    int64_t row_stride;
+    int32_t nodes, blocks;         // blocks: ids 0..max_id
+    const int32_t* row_of;         // [nodes]
+    const int64_t* blk_lo;         // [blocks]
+    const int64_t* blk_hi;
+    const uint8_t* held;           // [rows][blocks] kMafHeld | kMafForward
+    const int32_t* size;           // [rows][blocks] characters that are neither '-' nor 'x' (0 when not held)
+    const int32_t* col_main;       // [columns]
+    const int32_t* col_first;      // [columns]
+    const int32_t* rev_top;        // [blocks] the main column of position n_0 in the block; -1: none
+    int64_t start, end;            // the global coordinates
+    AaSpan* span;                  // [nodes]
+};
+hipError_t launch_aa_locate(pm_ctx* c, const AaArgs& a);
+// The codon tables of nodes node[0 .. n): slot s holds bases (2-bit codes in TCAG order, one
+// byte each) at base + s * base_cap and the codons' window indices at cstart / cend + s * codon_cap.
+struct AaTables {
+    int32_t n;
+    const int32_t* node;           // [n]
+    int32_t base_cap, codon_cap;
+    uint8_t* base;
+    int32_t* cstart;
+    int32_t* cend;
+    int32_t* codons;               // [n] complete codons; 0 when the window is "ERROR"
+    uint8_t* error;                // [n] 1: the walk met no stop
+};
+hipError_t launch_aa_codons(pm_ctx* c, const AaArgs& a, const AaTables& t);
+// The lines of a batch against the root's tables (slot 0 of `root`).
+struct AaText {
+    const int64_t* name_off;       // [nodes + 1] into names
+    const char* names;
+    int64_t* line_len;             // [n] bytes of the slot's line; 0: no line
+    int32_t* sec;                  // [n][2] bytes of the line's S and I entries
+    const int64_t* line_off;       // [n] exclusive scan of line_len
+    char* text;
+};
+hipError_t launch_aa_line_len(pm_ctx* c, const AaArgs& a, const AaTables& root, const AaTables& t, const AaText& x);
+hipError_t launch_aa_write(pm_ctx* c, const AaArgs& a, const AaTables& root, const AaTables& t, const AaText& x);
+hipError_t warm_aa();
 // rows[leaf][c0 .. c0+n) chars -> packed codes out[leaf][(n+1)/2] ('-', 'x' -> 0)
 hipError_t launch_rows_to_codes(pm_ctx* c, const char* rows, int64_t row_stride, int32_t leaves, int64_t c0,
                                 int64_t n, uint8_t* out, int64_t out_stride);
