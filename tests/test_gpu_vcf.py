@@ -1,6 +1,7 @@
 """pm_vcf on the GPU against the Python reference (tests/_vcf_ref.py, pinned to src/vcf.cpp:177-382
 by tests/test_vcf_ref.py) run on the rows of Engine.fasta(pm, aligned=True), the oracle-pinned
 path.  The ##fileDate line is masked; everything else is compared byte for byte."""
+import functools
 import os
 import subprocess
 import threading
@@ -11,7 +12,10 @@ import pytest
 import panman_amd
 from _panmat import parse_records, random_panmat
 from _trees import names_for, parse_newick, random_tree, to_newick
-from _vcf_cases import edge_rows, modal_reference, random_case, star_panmat
+from _vcf_cases import (GAPPED_CASES, MANY_ALTS_TIPS, MANY_RECORDS, ROUND_CASES, check_gapped_rows,
+                        check_many_alts_rows, check_many_records_rows, check_no_record_rows, check_round_rows,
+                        edge_rows, gapped_rows, many_alts_rows, many_records_rows, modal_reference, no_record_rows,
+                        random_case, round_rows, star_panmat)
 from _vcf_ref import mask_date, records, scan, vcf
 from panman_amd.panmat import write_panman
 from test_vcf_ref import CASES
@@ -32,6 +36,20 @@ def _rows(engine, pm):
     return parse_records(engine.fasta(pm, True))
 
 
+def _same_text(got, want):
+    """got == want, failing with the first differing line alone (pytest's diff of two long texts
+    that differ on many lines runs for minutes)."""
+    if got == want:
+        return
+    g, w = got.split("\n"), want.split("\n")
+    k = next((i for i, (x, y) in enumerate(zip(g, w)) if x != y), min(len(g), len(w)))
+    x, y = (t[k] if k < len(t) else None for t in (g, w))
+    at = None if x is None or y is None else next((i for i, (a, b) in enumerate(zip(x, y)) if a != b), min(len(x), len(y)))
+    show = [t if t is None else t[max(0, (at or 0) - 60):(at or 0) + 60] for t in (x, y)]
+    pytest.fail(f"line {k} (of {len(g)} / {len(w)}), byte {at}: "
+                f"got {show[0]!r}, want {show[1]!r}", pytrace=False)
+
+
 def _check(engine, pm, reference, rows=None):
     """Engine.vcf == the Python reference on the engine's aligned rows; returns (text, skipped)."""
     got_rows = _rows(engine, pm)
@@ -39,7 +57,7 @@ def _check(engine, pm, reference, rows=None):
         assert got_rows == rows
     want, wskip = vcf(got_rows, reference)
     got, gskip = engine.vcf(pm, reference)
-    assert mask_date(got) == mask_date(want)
+    _same_text(mask_date(got), mask_date(want))
     assert got.split("\n")[1] == want.split("\n")[1]   # (the date itself, barring midnight)
     assert gskip == wskip
     return got, gskip
@@ -48,7 +66,7 @@ def _check(engine, pm, reference, rows=None):
 # ---- hand cases --------------------------------------------------------------------------
 
 def _hand_trees():
-    """The fourteen cases' rows as the tips of two one-block trees (four and five columns)."""
+    """The hand cases' rows as the tips of two one-block trees (four and five columns)."""
     trees = {}
     for ref, tip, _ in CASES:
         for row in (ref, tip):
@@ -152,6 +170,121 @@ def test_edges(engine, columns, tips, ref_name):
     assert skipped == 0 and len(text.split("\n")) > 7
 
 
+# ---- the kernels' rounds, waves and digits (the constants are named in tests/_vcf_cases.py) ------
+
+def _small_batches(engine, pm, reference):
+    engine.set_vcf_batch_bytes(4096)
+    try:
+        return engine.vcf(pm, reference)
+    finally:
+        engine.set_vcf_batch_bytes(1 << 30)
+
+
+def _data(text):
+    return [line.split("\t") for line in text.split("\n")[5:-1]]
+
+
+@pytest.mark.parametrize("columns,ref_name,ref_gap", ROUND_CASES)
+def test_round_edges(engine, columns, ref_name, ref_gap):
+    """1024 = kVcfWaveWords (16) words: one k_vcf_classify wave; 4096 = 64 words: one k_vcf_starts
+    round and one classify workgroup; 8192: two of them; every 2048 = 256 x kRefItems (8) columns
+    one k_vcf_ref round."""
+    rows, cons = round_rows(columns, seed=columns, ref_name=ref_name, ref_gap=ref_gap)
+    check_round_rows(rows, ref_name, columns, ref_gap)
+    text, skipped = _check(engine, star_panmat(rows, cons), ref_name, rows)
+    assert skipped == 0 and len(_data(text)) > 7
+
+
+@pytest.fixture(scope="module")
+def round_case(engine):
+    """The 8193-column case of ROUND_CASES with the reference last."""
+    rows, cons = round_rows(8193, seed=8193, ref_name="z_ref")
+    return star_panmat(rows, cons), rows, "z_ref"
+
+
+@functools.lru_cache(maxsize=None)
+def _gapped_case(columns, run, end):
+    rows, cons = gapped_rows(columns, run, seed=run, end=end)
+    check_gapped_rows(rows, columns, run, end)
+    return star_panmat(rows, cons), rows
+
+
+def _insert_lines(text, run):
+    """The lines of the "insert" tip's insertions of `run` bases (the second run has min(run, 130))."""
+    samples = text.split("\n")[4].split("\t")[9:]
+    col = 9 + samples.index("insert")
+    found = [f for f in _data(text) if any(len(a) == run + 1 for a in f[4].split(","))]
+    assert len(found) == (2 if run <= 130 else 1)
+    for f in found:
+        assert len(f[3]) == 1 and f[col] != "0" and len(f[4].split(",")[int(f[col]) - 1]) == run + 1
+    return ["\t".join(f) for f in found]
+
+
+@pytest.mark.parametrize("columns,run,end", GAPPED_CASES)
+def test_gapped_runs(engine, columns, run, end):
+    """Runs of columns that are gaps in both rows below an event: within one word (63), over whole
+    words (64, 65, 130) and over a whole k_vcf_starts round of 64 words (4096)."""
+    pm, rows = _gapped_case(columns, run, end)
+    text, skipped = _check(engine, pm, "ref", rows)
+    assert skipped == 0
+    _insert_lines(text, run)
+
+
+def test_a_line_longer_than_the_batch(engine):
+    columns, run, end = GAPPED_CASES[-1]
+    pm, rows = _gapped_case(columns, run, end)
+    want, wskip = _check(engine, pm, "ref", rows)
+    got, gskip = _small_batches(engine, pm, "ref")
+    _same_text(got, want)
+    assert gskip == wskip
+    assert run == 4096 and len(_insert_lines(got, run)[0]) > 4096   # (the batch bytes as set)
+
+
+def test_three_digit_genotypes(engine):
+    rows, cons = many_alts_rows(MANY_ALTS_TIPS)
+    alts, samples, prefix = check_many_alts_rows(rows)
+    pm = star_panmat(rows, cons)
+    text, skipped = _check(engine, pm, "r", rows)
+    data = _data(text)
+    assert skipped == 0 and len(data) == 1 and len(data[0]) == 9 + samples
+    assert len("\t".join(data[0][:9])) == prefix > 256
+    assert {len(g) for g in data[0][9:9 + 256]} == {len(g) for g in data[0][9 + 256:]} == {1, 2, 3}
+    assert max(int(g) for g in data[0][9:]) == alts
+    got, gskip = _small_batches(engine, pm, "r")
+    _same_text(got, text)
+    assert gskip == skipped
+
+
+def test_many_records_sorted_in_pieces(engine, monkeypatch):
+    """The host's sort in 1, 2 and 8 pieces (PM_HOST_THREADS; kPiece = 1024 records), and its
+    comparator on records that share the 64-bit key (POS, REF[:4])."""
+    rows, cons = many_records_rows(*MANY_RECORDS)
+    nrec, lines, _ = check_many_records_rows(rows)
+    pm = star_panmat(rows, cons)
+    want, _ = _check(engine, pm, "ref", rows)
+    for threads in ("1", "2", "8"):
+        monkeypatch.setenv("PM_HOST_THREADS", threads)
+        panman_amd.phase_reset()
+        got, skipped = engine.vcf(pm, "ref")
+        report = dict(panman_amd.phase_report())
+        _same_text(got, want)
+        assert skipped == 0, threads
+        assert (report["vcf.records"], report["vcf.lines"]) == (nrec, lines), threads
+    assert len(_data(want)) == lines
+
+
+def test_no_events_and_no_records(engine):
+    cases = no_record_rows()
+    check_no_record_rows(cases)
+    for rows, cons, reference in cases:
+        text, skipped = _check(engine, star_panmat(rows, cons), reference, rows)
+        assert skipped == 0 and _data(text) == [] and len(text.split("\n")) == 6
+    ref, tip, want = CASES[7]   # the context still serves an ordinary case
+    rows = _hand_trees()[len(ref)]
+    text, _ = _check(engine, star_panmat(rows, "ACGTA"[:len(ref)]), f"row_{ref}", rows)
+    assert want and len(_data(text)) > 0
+
+
 # ---- batches, descriptors ----------------------------------------------------------------------
 
 def test_batches_give_the_same_text(engine, big_case):
@@ -167,8 +300,7 @@ def test_batches_give_the_same_text(engine, big_case):
         engine.set_vcf_batch_bytes(4095)
 
 
-def test_vcf_fd_into_a_pipe(engine, big_case):
-    pm, _, reference = big_case
+def _through_a_pipe(engine, pm, reference):
     want, wskip = engine.vcf(pm, reference)
     r, w = os.pipe()
     chunks = []
@@ -190,6 +322,18 @@ def test_vcf_fd_into_a_pipe(engine, big_case):
         os.close(r)
     got = b"".join(chunks)
     assert got == want.encode() and length == len(got) and skipped == wskip
+    return want
+
+
+def test_vcf_fd_into_a_pipe(engine, big_case):
+    pm, _, reference = big_case
+    _through_a_pipe(engine, pm, reference)
+
+
+def test_vcf_fd_of_a_multi_round_row(engine, round_case):
+    pm, rows, reference = round_case
+    want = _through_a_pipe(engine, pm, reference)
+    _same_text(mask_date(want), mask_date(vcf(rows, reference)[0]))
 
 
 # ---- errors --------------------------------------------------------------------------------------

@@ -20,6 +20,12 @@ CASES = [
     ("A-CT", "A--T", [(1, "AC", "A")]),
     ("ACGT", "A-TT", [(1, "ACG", "AT")]),
     ("AC-GT", "A-CTT", [(3, "G", "T")]),
+    # columns that are gaps in both rows, inside and in front of an event
+    ("AC-GT", "AT-TT", [(2, "CG", "TT")]),                   # one event across the both-gap column
+    ("A--CT", "A---T", [(1, "AC", "A")]),                    # the anchor from before a both-gap run
+    ("AC--T", "AC-GT", [(2, "C", "CG")]),                    # ... and an insertion behind it
+    ("-C-GT", "AC-TT", [(1, "C", "AC"), (2, "G", "T")]),     # after the leading insertion the strings are
+    ("-C-GT", "AC--T", [(1, "C", "AC"), (2, "G", "")]),      # empty: no anchor across the both-gap column
 ]
 
 
