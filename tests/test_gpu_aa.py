@@ -2,7 +2,9 @@
 src/aaTrans.cpp:185-304 by tests/test_aa_ref.py): the hand cases, random PanMATs, and the kernels'
 edges -- window lengths around a wave and around k_aa_codons' round of cells, codons that straddle
 a round, a node without codons, four-digit indices, names of different lengths, batches, a pipe,
-errors, the header, the facade."""
+errors, the header, the facade; then the shapes of tests/_aa_cases.py that cross a kernel constant
+away from the single forward block: blocks of 300 bases on both strands with gap slots, 129 blocks,
+258 nodes, five-digit indices."""
 import os
 import re
 import subprocess
@@ -12,7 +14,9 @@ import pytest
 
 import panman_amd
 import _aa_ref
-from _aa_cases import HAND, ND, RANDOM, SNP_DEL, issue_case, random_case, star, text_of, unsupported_case
+from _aa_cases import (HAND, MANY_BLOCKS_WINDOWS, ND, RANDOM, SNP_DEL, WIDE_CASES, WIDE_ERRORS, WIDE_WINDOWS,
+                       check_five_digit_case, five_digit_case, issue_case, many_blocks_case, many_nodes_case, random_case,
+                       star, text_of, unsupported_case, wide_case)
 from panman_amd.panmat import PanmanFile, write_panman
 from test_aa_ref import _window
 
@@ -152,8 +156,8 @@ def test_batches_give_the_same_text(engine):
         engine.set_aa_batch_bytes(4095)
 
 
-def test_aa_fd_into_a_pipe(engine, long_star):
-    want = _aa_ref.aa(long_star, 3, 640)
+def _through_a_pipe(engine, pm, start, end):
+    """engine.aa_fd into a pipe that a thread drains: (the bytes read, aa_fd's result)."""
     r, w = os.pipe()
     chunks = []
 
@@ -167,13 +171,108 @@ def test_aa_fd_into_a_pipe(engine, long_star):
     t = threading.Thread(target=drain)
     t.start()
     try:
-        length, ref_codons, unlocated = engine.aa_fd(long_star, 3, 640, w)
+        result = engine.aa_fd(pm, start, end, w)
     finally:
         os.close(w)
         t.join()
         os.close(r)
-    got = b"".join(chunks)
+    return b"".join(chunks), result
+
+
+def test_aa_fd_into_a_pipe(engine, long_star):
+    want = _aa_ref.aa(long_star, 3, 640)
+    got, (length, ref_codons, unlocated) = _through_a_pipe(engine, long_star, 3, 640)
     assert got == want[0].encode() and (length, ref_codons, unlocated) == (len(got), want[1], want[2])
+
+
+# ---- the rounds, waves and carries of the kernels (the builders and their checks: tests/_aa_cases.py,
+# ---- tests/test_aa_cases.py) ---------------------------------------------------------------------------
+
+def _assert_same(got, want, where=()):
+    """got == want for (text, root codons, unlocated), naming the first line that differs and its
+    node (pytest's own diff of two 100 KB strings takes minutes)."""
+    assert got[1:] == want[1:], (where, got[1:], want[1:])
+    if got[0] == want[0]:
+        return
+    g, w = got[0].split("\n"), want[0].split("\n")
+    for n in range(max(len(g), len(w))):
+        a, b = (g[n] if n < len(g) else None), (w[n] if n < len(w) else None)
+        if a == b:
+            continue
+        at = next((k for k in range(min(len(a or ""), len(b or ""))) if a[k] != b[k]), min(len(a or ""), len(b or "")))
+        cut = lambda s: None if s is None else s[max(0, at - 30):at + 50]
+        node = (b if b is not None else a).partition("\t")[0]
+        pytest.fail(f"{where}: line {n} (node {node!r}) differs at byte {at}: got {cut(a)!r} (of {len(a or '')}), "
+                    f"want {cut(b)!r} (of {len(b or '')}); {len(g)} lines against {len(w)}", pytrace=False)
+
+
+@pytest.mark.parametrize("strands,ids,slots", WIDE_CASES)
+def test_wide_windows(engine, strands, ids, slots):
+    """Blocks wider than a round of both kernels on both strands: second and later rounds of the
+    backward rank-select and of the backward walk, rounds with unwalked cells before walked ones,
+    an absent block of 300 dashes inside a codon, ids that hold no block, coordinates that wrap
+    on one node alone."""
+    pm = wide_case(strands, ids, slots)
+    for start, end in WIDE_WINDOWS[strands, slots]:
+        _assert_same(engine.aa(pm, start, end), _aa_ref.aa(pm, start, end), (start, end))
+
+
+@pytest.mark.parametrize("strands,slots", list(WIDE_ERRORS))
+def test_wide_error_windows(engine, strands, slots):
+    """The root's window never reaches its end -- on a slot the walk leaves out beyond the first
+    round, or wrapped in front of the start: rc=-1, and the context goes on."""
+    pm = wide_case(strands, (0, 2, 5), slots)
+    for start, end in WIDE_ERRORS[strands, slots]:
+        with pytest.raises(panman_amd.PanmanError) as err:
+            engine.aa(pm, start, end)
+        assert "rc=-1" in str(err.value), (start, end)
+    start, end = WIDE_WINDOWS[strands, slots][0]
+    _assert_same(engine.aa(pm, start, end), _aa_ref.aa(pm, start, end), (start, end))
+
+
+def test_block_scan_round_edges(engine):
+    """129 blocks: starts and ends in blocks 63 | 64 | 65 and 127 | 128, the last lane of a round of
+    k_aa_locate's block scan and the first of the next."""
+    pm = many_blocks_case()
+    for start, end in MANY_BLOCKS_WINDOWS:
+        _assert_same(engine.aa(pm, start, end), _aa_ref.aa(pm, start, end), (start, end))
+
+
+def test_five_digit_indices(engine):
+    """10,020 root codons: S:1dddd and I:10020 entries, a line of more than 65,536 bytes -- also
+    through a pipe, whose buffer is shorter than that line."""
+    pm, start, end = five_digit_case()
+    want = _aa_ref.aa(pm, start, end)
+    check_five_digit_case(want)
+    _assert_same(engine.aa(pm, start, end), want)
+    got, (length, ref_codons, unlocated) = _through_a_pipe(engine, pm, start, end)
+    _assert_same((got.decode(), ref_codons, unlocated), want, "pipe")
+    assert length == len(got)
+
+
+def test_many_nodes(engine):
+    """258 nodes: k_aa_locate's last workgroup has two of its four waves."""
+    pm, start, end = many_nodes_case()
+    _assert_same(engine.aa(pm, start, end), _aa_ref.aa(pm, start, end))
+
+
+def test_wide_batches(engine):
+    """Batches of one node over a wide case: "same" prints nothing between two nodes that do, so
+    a batch without bytes lies between two with bytes."""
+    strands, ids, slots = "+-+", (0, 2, 5), True
+    pm = wide_case(strands, ids, slots)
+    assert pm.names.index("lost") + 1 == pm.names.index("same") == pm.names.index("flip_middle") - 1
+    between = 0
+    engine.set_aa_batch_bytes(4096)
+    try:
+        for start, end in WIDE_WINDOWS[strands, slots]:
+            want = _aa_ref.aa(pm, start, end)
+            if end - start > 150:   # one node's tables fill a 4096-byte batch
+                between += "\nlost\t" in want[0] and "\nflip_middle\t" in want[0] and "\nsame\t" not in want[0]
+            _assert_same(engine.aa(pm, start, end), want, (start, end))
+    finally:
+        engine.set_aa_batch_bytes(1 << 30)
+    assert between >= 5
 
 
 # ---- errors --------------------------------------------------------------------------------------
