@@ -26,7 +26,7 @@
 #include <cstdlib>
 #include <vector>
 
-#include "pm_internal.h"
+#include "pm_plan.h"
 
 namespace pm {
 

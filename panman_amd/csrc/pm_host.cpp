@@ -1,14 +1,13 @@
-// pm_host.cpp -- host side of the C-ABI: context, tree flattening, uploads, results.
+// pm_host.cpp -- host side of the C-ABI: context, uploads, results.
 //
 // The reference keeps the tree as Node* with children vectors and rebuilds an
 // unordered_map<string,int> per column (src/panman.cpp:1409-1417).  Here the topology is
-// flattened once (pm_tree_upload): dense internal indices, height levels for the
-// post-order and depth levels for the pre-order, children encoded for the kernels.
+// flattened once (pm_tree_upload: the host plan of pm_plan.cpp, then its arrays to the
+// device): dense internal indices, height levels for the post-order and depth levels for
+// the pre-order, children encoded for the kernels.
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
-#include <random>
 #include <cstring>
 #include <numeric>
 #include <string>
@@ -50,50 +49,77 @@ hipError_t upload(T** dst, const std::vector<T>& v, hipStream_t s) {
     return hipStreamSynchronize(s);   // host vectors may die after return
 }
 
+// Every device array of the tree, in upload order: X(DevTree pointer, its host vector in a
+// TreePlan p).  The one list behind free_tree and upload_tree.
+#define PM_TREE_ARRAYS(X)                 \
+    X(child_off, p.ht.child_off)          \
+    X(child_enc, p.ht.child_enc)          \
+    X(parent_dense, p.parent_dense)       \
+    X(internal_id, p.ht.internal_id)      \
+    X(leaf_id, p.ht.leaf_id)              \
+    X(up_order, p.up_order)               \
+    X(down_order, p.down_order)           \
+    X(leaf_parent, p.leaf_parent)         \
+    X(leaf_down, p.leaf_down)             \
+    X(child_enc_v, p.child_enc_v)         \
+    X(up_order_v, p.up_order_v)           \
+    X(down_order_v, p.down_order_v)       \
+    X(down_desc, p.down_desc)             \
+    X(up_desc, p.up_desc)                 \
+    X(up_desc_v, p.up_desc_v)             \
+    X(down_desc_v, p.down_desc_v)         \
+    X(vleaf, p.vleaf)                     \
+    X(tail_desc, p.tail_desc)             \
+    X(tail_desc_v, p.tail_desc_v)         \
+    X(part_desc, p.part_desc)             \
+    X(part_desc_v, p.part_desc_v)         \
+    X(part_desc_k, p.part_desc_k)         \
+    X(part_desc_gs, p.part_desc_gs)       \
+    X(child_enc_k, p.child_enc_k)         \
+    X(up_desc_k, p.up_desc_k)             \
+    X(up_desc_g, p.up_desc_g)             \
+    X(up_desc_gs, p.up_desc_gs)           \
+    X(down_desc_k, p.down_desc_k)         \
+    X(down_desc_ks, p.down_desc_ks)       \
+    X(pslot_k, p.pslot_k)                 \
+    X(pslot_g, p.pslot_g)                 \
+    X(pslot_gs, p.pslot_gs)               \
+    X(vinner, p.vinner)                   \
+    X(tail_desc_k, p.tail_desc_k)         \
+    X(lvl, p.lvl)                         \
+    X(cl_items, p.ht.cl.items)            \
+    X(cl_down_items, p.ht.cl.down_items)  \
+    X(cl_wg_off, p.ht.cl.wg_off)          \
+    X(cl_slot_of, p.ht.cl.slot_of)        \
+    X(pslot_kc, p.pslot_kc)               \
+    X(pslot_gc, p.pslot_gc)               \
+    X(cl_pslot, p.cl_pslot)
+
 void free_tree(DevTree& t) {
-    dev_free(t.child_off);
-    dev_free(t.child_enc);
-    dev_free(t.parent_dense);
-    dev_free(t.internal_id);
-    dev_free(t.leaf_id);
-    dev_free(t.up_order);
-    dev_free(t.down_order);
-    dev_free(t.leaf_parent);
-    dev_free(t.leaf_down);
-    dev_free(t.child_enc_v);
-    dev_free(t.up_order_v);
-    dev_free(t.down_order_v);
-    dev_free(t.down_desc);
-    dev_free(t.up_desc);
-    dev_free(t.up_desc_v);
-    dev_free(t.down_desc_v);
-    dev_free(t.tail_desc);
-    dev_free(t.tail_desc_v);
-    dev_free(t.vleaf);
-    dev_free(t.part_desc);
-    dev_free(t.part_desc_v);
-    dev_free(t.part_desc_k);
-    dev_free(t.part_desc_gs);
-    dev_free(t.child_enc_k);
-    dev_free(t.up_desc_k);
-    dev_free(t.up_desc_g);
-    dev_free(t.up_desc_gs);
-    dev_free(t.down_desc_k);
-    dev_free(t.down_desc_ks);
-    dev_free(t.pslot_k);
-    dev_free(t.pslot_g);
-    dev_free(t.pslot_gs);
-    dev_free(t.vinner);
-    dev_free(t.tail_desc_k);
-    dev_free(t.lvl);
-    dev_free(t.cl_items);
-    dev_free(t.cl_down_items);
-    dev_free(t.cl_wg_off);
-    dev_free(t.cl_slot_of);
-    dev_free(t.pslot_kc);
-    dev_free(t.pslot_gc);
-    dev_free(t.cl_pslot);
+#define X(field, host) dev_free(t.field);
+    PM_TREE_ARRAYS(X)
+#undef X
     t = DevTree{};
+}
+
+// The plan's arrays on the device and their bytes (pm_memory_footprint); on a failure nothing
+// stays allocated.
+hipError_t upload_tree(const TreePlan& p, hipStream_t s, DevTree& dt, size_t& bytes) {
+    dt = DevTree{};
+    dt.num_internal = (int32_t)p.ht.internal_id.size();
+    dt.num_leaves = (int32_t)p.ht.leaf_id.size();
+    dt.root_dense = p.ht.dense_of[p.ht.root];
+    bytes = 0;
+    hipError_t e = hipSuccess;
+#define X(field, host)                                  \
+    if (e == hipSuccess) {                              \
+        bytes += sizeof((host)[0]) * (host).size();     \
+        e = upload(&dt.field, host, s);                 \
+    }
+    PM_TREE_ARRAYS(X)
+#undef X
+    if (e != hipSuccess) free_tree(dt);
+    return e;
 }
 
 void drop_graph(pm_ctx* c) {
@@ -613,733 +639,36 @@ int pm_set_profiling(pm_ctx* c, int enable) {
 }
 
 int pm_tree_upload(pm_ctx* c, const pm_tree* t) {
-    // PM_UPLOAD_TIMING=1: host phase durations on stderr
-    const bool timing = std::getenv("PM_UPLOAD_TIMING") != nullptr;
-    auto t_last = std::chrono::steady_clock::now();
-    auto upload_phase = [&](const char* what) {
-        const auto now = std::chrono::steady_clock::now();
-        phase_add(std::string("tree.") + what, std::chrono::duration<double>(now - t_last).count());
-        if (!timing) {
-            t_last = now;
-            return;
-        }
-        std::fprintf(stderr, "[pm_tree_upload] %-16s %8.2f s\n", what, std::chrono::duration<double>(now - t_last).count());
-        t_last = now;
-    };
     if (!c || !t || !t->child_offsets || t->num_nodes < 2) return fail(c, PM_ERR_ARG, "bad tree");
     (void)hipSetDevice(c->device);
     c->sub_planes_ok = false;   // its S2 / S3 nodes are this tree's
-    const int32_t N = t->num_nodes;
-    const int32_t* off = t->child_offsets;
-    const int32_t* idx = t->child_index;
-    if (off[0] != 0 || t->root < 0 || t->root >= N) return fail(c, PM_ERR_ARG, "bad tree header");
-    for (int32_t i = 0; i < N; ++i)
-        if (off[i + 1] < off[i]) return fail(c, PM_ERR_ARG, "child offsets not monotone");
-    const int32_t E = off[N];
-    if (E != N - 1) return fail(c, PM_ERR_ARG, "a tree on N nodes has N-1 edges");
-    std::vector<int32_t> parent(N, -2);
-    parent[t->root] = -1;
-    for (int32_t i = 0; i < N; ++i)
-        for (int32_t e = off[i]; e < off[i + 1]; ++e) {
-            const int32_t ch = idx[e];
-            if (ch < 0 || ch >= N || parent[ch] != -2) return fail(c, PM_ERR_ARG, "child index invalid or repeated");
-            parent[ch] = i;
-        }
-    if (off[t->root + 1] == off[t->root]) return fail(c, PM_ERR_ARG, "root must be internal");
-    // a child's encoding keeps the dense internal index in its low kShapeShift bits (the
-    // subtree shape above them): more internal nodes would mix shape bits into indices
-    int64_t internal = 0;
-    for (int32_t i = 0; i < N; ++i) internal += off[i + 1] > off[i];
-    if (internal > kDenseMask) return fail(c, PM_ERR_ARG, "too many internal nodes (limit 2^28 - 1)");
-    // BFS from the root: depth + connectivity.
-    std::vector<int32_t> bfs;
-    bfs.reserve(N);
-    std::vector<int32_t> depth(N, -1);
-    bfs.push_back(t->root);
-    depth[t->root] = 0;
-    for (size_t h = 0; h < bfs.size(); ++h) {
-        const int32_t u = bfs[h];
-        for (int32_t e = off[u]; e < off[u + 1]; ++e) {
-            depth[idx[e]] = depth[u] + 1;
-            bfs.push_back(idx[e]);
-        }
-    }
-    if ((int32_t)bfs.size() != N) return fail(c, PM_ERR_ARG, "tree is not connected");
-    std::vector<int32_t> height(N, 0);
-    for (int32_t k = N - 1; k >= 0; --k) {
-        const int32_t u = bfs[k];
-        int32_t h = 0;
-        for (int32_t e = off[u]; e < off[u + 1]; ++e) h = std::max(h, height[idx[e]] + 1);
-        height[u] = off[u + 1] > off[u] ? h : 0;
-    }
-
-    HostTree ht;
-    ht.num_nodes = N;
-    ht.root = t->root;
-    ht.dense_of.assign(N, 0);
-    // Dense internal indices and leaf ranks in DFS pre-order: a subtree's leaf rows and
-    // records are contiguous, and the nodes of one level (bucketed in dense order below)
-    // run in tree order, so neighbouring waves read neighbouring rows.
-    std::vector<int32_t> dfs;
-    dfs.reserve(N);
-    {
-        std::vector<int32_t> stack{t->root};
-        while (!stack.empty()) {
-            const int32_t u = stack.back();
-            stack.pop_back();
-            dfs.push_back(u);
-            for (int32_t e = off[u + 1] - 1; e >= off[u]; --e) stack.push_back(idx[e]);
-        }
-    }
-    // Internal nodes: the materialised ones (every internal node but the virtual
-    // leaf-parents, see below) by depth, then the virtual ones; DFS order within a depth.
-    // A pre-order level of the virtual-leaf-parent form is then a contiguous range of
-    // dense indices, so its waves know their node -- and its record masks -- without
-    // reading the level descriptor first (DevTree::down_dense).
-    auto virtual_id = [&](int32_t u) {
-        if (u == t->root || off[u + 1] == off[u] || off[u + 1] - off[u] > 2) return false;
-        for (int32_t e = off[u]; e < off[u + 1]; ++e)
-            if (off[idx[e] + 1] > off[idx[e]]) return false;
-        return true;
-    };
-    // Subtree form (Fitch, every leaf present): a node whose two children are leaves or
-    // two-leaf cherries, at least one a cherry, under a parent of out-degree <= 2, is also
-    // evaluated inline by its parent (shapes S2 = (cherry, leaf), S3 = (cherry, cherry)).
-    auto cherry2 = [&](int32_t u) {
-        return u != t->root && off[u + 1] - off[u] == 2 && off[idx[off[u]] + 1] == off[idx[off[u]]] &&
-               off[idx[off[u] + 1] + 1] == off[idx[off[u] + 1]];
-    };
-    auto sshape_id = [&](int32_t u) {
-        if (u == t->root || off[u + 1] - off[u] != 2 || parent[u] < 0 || off[parent[u] + 1] - off[parent[u]] > 2)
-            return 0;
-        int cherries = 0;
-        for (int32_t e = off[u]; e < off[u + 1]; ++e) {
-            const int32_t ch = idx[e];
-            if (off[ch + 1] == off[ch]) continue;
-            if (!cherry2(ch)) return 0;
-            ++cherries;
-        }
-        return cherries;   // 1: S2, 2: S3
-    };
-    {
-        std::vector<int32_t> inner;
-        for (const int32_t i : dfs) {
-            if (off[i + 1] > off[i]) {
-                inner.push_back(i);
-            } else {
-                ht.dense_of[i] = -(int32_t)ht.leaf_id.size() - 1;
-                ht.leaf_id.push_back(i);
-            }
-        }
-        // stable counting sort by key: DFS order kept within a key
-        int32_t maxd = 0;
-        for (const int32_t i : inner) maxd = std::max(maxd, depth[i]);
-        // key: the materialised nodes by (depth, has an S2 / S3 child) -- a subtree-form
-        // pre-order level, and each half of it, is one contiguous range of dense indices --
-        // then the S2 / S3 nodes by depth -- the order of the subtree form's tail items, so a
-        // tail wave knows its S2 / S3 node, and the masks its parent pushed there, from its
-        // item index alone -- then the virtual leaf-parents.  (The leaf-parent form's levels,
-        // which include the S2 / S3 nodes, are then two ranges: its pre-order kernels read
-        // the node from the descriptor.)
-        auto has_sub_child = [&](int32_t u) {
-            for (int32_t e = off[u]; e < off[u + 1]; ++e)
-                if (sshape_id(idx[e])) return true;
-            return false;
-        };
-        const int32_t D1 = maxd + 1, nk = 4 * D1;
-        std::vector<int32_t> key(inner.size()), start(nk + 1, 0);
-        for (size_t k = 0; k < inner.size(); ++k) {
-            const int32_t u = inner[k];
-            key[k] = virtual_id(u) ? 3 * D1 + depth[u] : sshape_id(u) ? 2 * D1 + depth[u]
-                                                       : 2 * depth[u] + (has_sub_child(u) ? 1 : 0);
-            ++start[key[k] + 1];
-        }
-        for (int32_t k = 0; k < nk; ++k) start[k + 1] += start[k];
-        ht.internal_id.assign(inner.size(), 0);
-        for (size_t k = 0; k < inner.size(); ++k) ht.internal_id[start[key[k]]++] = inner[k];
-        for (size_t k = 0; k < ht.internal_id.size(); ++k) ht.dense_of[ht.internal_id[k]] = (int32_t)k;
-    }
-    const int32_t I = (int32_t)ht.internal_id.size();
-    const int32_t L = (int32_t)ht.leaf_id.size();
-    // child encodings keep the dense index in the low kShapeShift bits (shape and virtual
-    // flags above it)
-    if (I >= (1 << kShapeShift)) return fail(c, PM_ERR_ARG, "trees of 2^28 or more internal nodes are not supported");
-    ht.child_off.assign(I + 1, 0);
-    ht.child_enc.reserve(E);
-    std::vector<int32_t> parent_dense(I, -1), leaf_parent(L, -1);
-    for (int32_t d = 0; d < I; ++d) {
-        const int32_t u = ht.internal_id[d];
-        for (int32_t e = off[u]; e < off[u + 1]; ++e) {
-            const int32_t ch = idx[e];
-            ht.child_enc.push_back(ht.dense_of[ch]);
-            if (ht.dense_of[ch] >= 0) parent_dense[ht.dense_of[ch]] = d;
-            else leaf_parent[-ht.dense_of[ch] - 1] = d;
-        }
-        ht.child_off[d + 1] = (int32_t)ht.child_enc.size();
-    }
-    // post-order levels: internal nodes by height 1..H
-    int32_t H = 0, D = 0;
-    for (int32_t d = 0; d < I; ++d) {
-        H = std::max(H, height[ht.internal_id[d]]);
-        D = std::max(D, depth[ht.internal_id[d]]);
-    }
-    int32_t DL = 0;
-    for (int32_t l = 0; l < L; ++l) DL = std::max(DL, depth[ht.leaf_id[l]]);
-    auto bucket = [](int32_t levels, int32_t count, auto key, std::vector<int32_t>& offs, std::vector<int32_t>& order) {
-        offs.assign(levels + 1, 0);
-        for (int32_t i = 0; i < count; ++i) ++offs[key(i) + 1];
-        for (int32_t k = 0; k < levels; ++k) offs[k + 1] += offs[k];
-        order.assign(count, 0);
-        std::vector<int32_t> cur(offs.begin(), offs.end() - 1);
-        for (int32_t i = 0; i < count; ++i) order[cur[key(i)]++] = i;
-    };
-    std::vector<int32_t> up_order, down_order, leaf_down;
-    bucket(H * kDegreeClasses, I,
-           [&](int32_t d) {
-               return (height[ht.internal_id[d]] - 1) * kDegreeClasses +
-                      degree_class(ht.child_off[d + 1] - ht.child_off[d]);
-           },
-           ht.up_class_off, up_order);
-    ht.up_level_off.assign(H + 1, 0);
-    for (int32_t h = 0; h <= H; ++h) ht.up_level_off[h] = ht.up_class_off[h * kDegreeClasses];
-    bucket(D + 1, I, [&](int32_t d) { return depth[ht.internal_id[d]]; }, ht.down_level_off, down_order);
-    bucket(DL + 1, L, [&](int32_t l) { return depth[ht.leaf_id[l]]; }, ht.leaf_level_off, leaf_down);
-
-    upload_phase("topology+levels");
-    // heavy child first: the internal child with the largest subtree (a materialised one
-    // on ties) leads its parent's child list, so it is the next node down the parent's
-    // chain in both the plain and the virtual-leaf-parent form (children order is free:
-    // every pass combines children commutatively and records are sorted on fetch)
-    auto is_virtual = [&](int32_t d) {
-        if (ht.internal_id[d] == t->root) return false;
-        const int32_t deg = ht.child_off[d + 1] - ht.child_off[d];
-        if (deg > 2) return false;
-        for (int32_t e = ht.child_off[d]; e < ht.child_off[d + 1]; ++e)
-            if (ht.child_enc[e] >= 0) return false;
-        return true;
-    };
-    {
-        std::vector<int64_t> sub(N, 1);
-        for (int32_t k = N - 1; k >= 0; --k) {
-            const int32_t u = bfs[k];
-            for (int32_t e = off[u]; e < off[u + 1]; ++e) sub[u] += sub[idx[e]];
-        }
-        for (int32_t d = 0; d < I; ++d) {
-            int32_t best = -1;
-            int64_t best_key = -1;
-            for (int32_t e = ht.child_off[d]; e < ht.child_off[d + 1]; ++e) {
-                const int32_t x = ht.child_enc[e];
-                if (x < 0) continue;
-                const int64_t key = sub[ht.internal_id[x]] * 2 + (is_virtual(x) ? 0 : 1);
-                if (key > best_key) { best_key = key; best = e; }
-            }
-            if (best > ht.child_off[d]) std::swap(ht.child_enc[best], ht.child_enc[ht.child_off[d]]);
-        }
-    }
-
-    upload_phase("heavy child");
-    // virtual leaf-parents (Fitch level kernels)
-    std::vector<int32_t> child_enc_v(ht.child_enc), up_order_v, down_order_v, vleaf((size_t)I * 4, -1);
-    std::vector<uint8_t> virt(I, 0);
-    {
-        for (int32_t d = 0; d < I; ++d) {
-            if (ht.internal_id[d] == t->root) continue;
-            const int32_t deg = ht.child_off[d + 1] - ht.child_off[d];
-            bool all_leaves = deg <= 2;   // one or two leaves: Fitch and Sankoff evaluate them inline
-            for (int32_t e = ht.child_off[d]; e < ht.child_off[d + 1] && all_leaves; ++e) all_leaves = ht.child_enc[e] < 0;
-            virt[d] = all_leaves;
-            ht.num_virtual += all_leaves;
-        }
-        for (auto& x : child_enc_v)
-            if (x >= 0 && virt[x]) x |= kVirtualBit;
-        for (int32_t d = 0; d < I; ++d)
-            if (virt[d])
-                for (int32_t e = ht.child_off[d], k = 0; e < ht.child_off[d + 1]; ++e, ++k)
-                    vleaf[(size_t)d * 4 + k] = -ht.child_enc[e] - 1;
-        // levels keep their (height, degree class) buckets; virtual nodes are dropped
-        auto drop = [&](std::vector<int32_t>& order, std::vector<int32_t>& offs) {
-            std::vector<int32_t> o2, f2{0};
-            for (size_t k = 0; k + 1 < offs.size(); ++k) {
-                for (int32_t i = offs[k]; i < offs[k + 1]; ++i)
-                    if (!virt[order[i]]) o2.push_back(order[i]);
-                f2.push_back((int32_t)o2.size());
-            }
-            order.swap(o2);
-            offs.swap(f2);
-        };
-        bucket(H * kDegreeClasses, I,
-               [&](int32_t d) {
-                   return (height[ht.internal_id[d]] - 1) * kDegreeClasses +
-                          degree_class(ht.child_off[d + 1] - ht.child_off[d]);
-               },
-               ht.up_class_off_v, up_order_v);
-        drop(up_order_v, ht.up_class_off_v);
-        ht.up_level_off_v.assign(H + 1, 0);
-        for (int32_t h = 0; h <= H; ++h) ht.up_level_off_v[h] = ht.up_class_off_v[h * kDegreeClasses];
-        // levels whose nodes of out-degree <= 3 have only leaf / virtual children
-        ht.up_leafy_v.assign(H, 0);
-        for (int32_t h = 0; h < H; ++h) {
-            bool leafy = true;
-            for (int32_t i = ht.up_class_off_v[h * kDegreeClasses]; i < ht.up_class_off_v[h * kDegreeClasses + 1] && leafy; ++i)
-                for (int32_t e = ht.child_off[up_order_v[i]]; e < ht.child_off[up_order_v[i] + 1]; ++e)
-                    leafy &= child_enc_v[e] < 0 || (child_enc_v[e] & kVirtualBit) != 0;
-            ht.up_leafy_v[h] = leafy;
-        }
-        bucket(D + 1, I, [&](int32_t d) { return depth[ht.internal_id[d]]; }, ht.down_level_off_v, down_order_v);
-        drop(down_order_v, ht.down_level_off_v);
-        ht.down_dense_v = true;   // pre-order item k of the virtual form is dense index k
-        for (size_t k = 0; k < down_order_v.size(); ++k) ht.down_dense_v &= down_order_v[k] == (int32_t)k;
-    }
-
-    upload_phase("virtual form");
-    // subtree form (Fitch, all leaves present): S2 / S3 nodes dropped from the levels as well;
-    // child encodings carry the shape (kShapeShift), vleaf their leaves (a, b[, c[, d]]) and
-    // vinner their cherries (x[, y])
-    std::vector<int32_t> child_enc_k(child_enc_v), up_order_k, down_order_k, vinner((size_t)I * 2, -1);
-    std::vector<uint8_t> sshape(I, 0);
-    {
-        for (int32_t d = 0; d < I; ++d) {
-            const int sh = sshape_id(ht.internal_id[d]);
-            if (!sh) continue;
-            sshape[d] = (uint8_t)sh;
-            // leaves: the cherries' leaves first, then the lone leaf (S2)
-            int32_t nl = 0, ni = 0;
-            for (int32_t e = ht.child_off[d]; e < ht.child_off[d + 1]; ++e) {
-                const int32_t x = ht.child_enc[e];
-                if (x < 0) continue;
-                vinner[(size_t)d * 2 + ni++] = x;
-                for (int32_t f = ht.child_off[x]; f < ht.child_off[x + 1]; ++f) vleaf[(size_t)d * 4 + nl++] = -ht.child_enc[f] - 1;
-            }
-            for (int32_t e = ht.child_off[d]; e < ht.child_off[d + 1]; ++e)
-                if (ht.child_enc[e] < 0) vleaf[(size_t)d * 4 + nl++] = -ht.child_enc[e] - 1;
-            ht.num_sshape += 1;
-        }
-        for (auto& x : child_enc_k)
-            if (x >= 0 && !(x & kVirtualBit) && sshape[x]) x = (x | kVirtualBit) | (sshape[x] << kShapeShift);
-        auto keep = [&](std::vector<int32_t>& order, std::vector<int32_t>& offs, const std::vector<int32_t>& src_order,
-                        const std::vector<int32_t>& src_offs) {
-            order.clear();
-            offs.assign(1, 0);
-            for (size_t k = 0; k + 1 < src_offs.size(); ++k) {
-                for (int32_t i = src_offs[k]; i < src_offs[k + 1]; ++i)
-                    if (!sshape[src_order[i]]) order.push_back(src_order[i]);
-                offs.push_back((int32_t)order.size());
-            }
-        };
-        keep(up_order_k, ht.up_class_off_k, up_order_v, ht.up_class_off_v);
-        ht.up_level_off_k.assign(H + 1, 0);
-        for (int32_t h = 0; h <= H; ++h) ht.up_level_off_k[h] = ht.up_class_off_k[h * kDegreeClasses];
-        ht.up_leafy_k.assign(H, 0);
-        for (int32_t h = 0; h < H; ++h) {
-            bool leafy = true;
-            for (int32_t i = ht.up_class_off_k[h * kDegreeClasses]; i < ht.up_class_off_k[h * kDegreeClasses + 1] && leafy; ++i)
-                for (int32_t e = ht.child_off[up_order_k[i]]; e < ht.child_off[up_order_k[i] + 1]; ++e)
-                    leafy &= child_enc_k[e] < 0 || (child_enc_k[e] & kVirtualBit) != 0;
-            ht.up_leafy_k[h] = leafy;
-        }
-        keep(down_order_k, ht.down_level_off_k, down_order_v, ht.down_level_off_v);
-        // each subtree-form pre-order level is one dense range (dense key: depth, then S2/S3 last)
-        ht.down_dense_base_k.assign(ht.down_level_off_k.size() - 1, -1);
-        bool dense = true;
-        for (size_t l = 0; l + 1 < ht.down_level_off_k.size(); ++l) {
-            const int32_t a = ht.down_level_off_k[l], b = ht.down_level_off_k[l + 1];
-            if (a == b) continue;
-            for (int32_t i = a; i < b; ++i) dense &= down_order_k[i] == down_order_k[a] + (i - a);
-            ht.down_dense_base_k[l] = down_order_k[a];
-        }
-        ht.down_dense_k = dense;
-    }
-    ht.sshape = sshape;
-    upload_phase("subtree form");
-    // LDS-staged post-order sweeps of the subtree form (PM_OPT_CLUSTER, pm_cluster.cpp)
-    plan_clusters(ht, up_order_k, child_enc_k, parent_dense, vleaf, c->cluster_max_level, c->cluster_chain, ht.cl);
-    upload_phase("clusters");
-    // (counts: the sweeps' first level, bands, workgroups per tile, longest workgroup in rounds)
-    phase_add("cluster.first_level", (double)ht.cl.h0);
-    phase_add("cluster.bands", ht.cl.band_wg.empty() ? 0.0 : (double)(ht.cl.band_wg.size() - 1));
-    phase_add("cluster.workgroups", ht.cl.wg_off.empty() ? 0.0 : (double)(ht.cl.wg_off.size() - 1));
-    phase_add("cluster.max_rounds", (double)ht.cl.max_rounds);
-    auto make_desc = [&](const std::vector<int32_t>& order, const std::vector<int32_t>& enc) {
-        std::vector<NodeDesc> desc(order.size());
-        for (size_t k = 0; k < order.size(); ++k) {
-            const int32_t d = order[k];
-            NodeDesc& x = desc[k];
-            x = NodeDesc{};
-            x.node = d;
-            x.parent = parent_dense[d];
-            x.e0 = ht.child_off[d];
-            x.e1 = ht.child_off[d + 1];
-            x.c0 = enc[x.e0];
-            x.c1 = x.e1 - x.e0 > 1 ? enc[x.e0 + 1] : 0;
-            for (int j = 0; j < 4; ++j) {
-                x.vl0[j] = x.c0 >= 0 && (x.c0 & kVirtualBit) ? vleaf[(size_t)(x.c0 & kDenseMask) * 4 + j] : -1;
-                x.vl1[j] = x.e1 - x.e0 > 1 && x.c1 >= 0 && (x.c1 & kVirtualBit)
-                               ? vleaf[(size_t)(x.c1 & kDenseMask) * 4 + j] : -1;
-            }
-        }
-        return desc;
-    };
-    // pre-order descriptors carry the grandparent and great-grandparent (k_down level groups
-    // recompute the ancestors' finals)
-    auto with_gp = [&](std::vector<NodeDesc> desc) {
-        for (NodeDesc& x : desc) {
-            x.pad0 = x.parent >= 0 ? parent_dense[x.parent] : -1;
-            x.pad1 = x.pad0 >= 0 ? parent_dense[x.pad0] : -1;
-        }
-        return desc;
-    };
-    const std::vector<NodeDesc> down_desc = with_gp(make_desc(down_order, ht.child_enc));
-    const std::vector<NodeDesc> down_desc_v = with_gp(make_desc(down_order_v, child_enc_v));
-    const std::vector<NodeDesc> up_desc = make_desc(up_order, ht.child_enc);
-    const std::vector<NodeDesc> up_desc_v = make_desc(up_order_v, child_enc_v);
-    const std::vector<NodeDesc> up_desc_k = make_desc(up_order_k, child_enc_k);
-    // Grouped post-order launches of the subtree form (PM_OPT_UP_GROUP): a node of
-    // out-degree <= 3 joins the launch of its latest materialised children when each of
-    // those is of out-degree <= max_rc (Fitch 3; Sankoff 2: a recomputed child's Z0 is the
-    // AND-else-OR of its children only when it is binary), computed from earlier launches
-    // only, and among its first two children -- its wave recomputes them in registers
-    // (k_fitch_up / k_sankoff_up <.., GROUP>, the descriptor's pad0 / pad1 = their descriptor
-    // indices) -- otherwise the launch after.  Children come before parents in up_order_k
-    // (height order).  Only nodes of heights with at most kUpGroupNodes nodes join a child's
-    // launch: big levels fill the chip by themselves and pay for the recomputation (measured
-    // at N*).
-    // `levels`: only the subtree form's first `levels` post-order levels (Fitch with the LDS-staged
-    // sweeps: the levels below them; the sweeps take the rest).
-    const std::vector<int32_t>& up_order_k_all = up_order_k;
-    auto make_groups = [&](int32_t max_rc, std::vector<int32_t>& level_off, std::vector<int32_t>& class_off,
-                           std::vector<uint8_t>& leafy_out, std::vector<uint8_t>& recomp_out,
-                           std::vector<int32_t>& plain_out, int32_t levels) {
-        levels = std::min<int32_t>(levels, (int32_t)ht.up_level_off_k.size() - 1);
-        const std::vector<int32_t> up_order_k(up_order_k_all.begin(), up_order_k_all.begin() + ht.up_level_off_k[levels]);
-        auto is_mat = [](int32_t x) { return x >= 0 && !(x & kVirtualBit); };
-        auto narrow = [&](int32_t d) { return degree_class(ht.child_off[d + 1] - ht.child_off[d]) == 0; };
-        auto recomputable = [&](int32_t d) { return ht.child_off[d + 1] - ht.child_off[d] <= max_rc; };
-        std::vector<int32_t> lv(I, -1), inl((size_t)I * 2, -1), hsize(I, 0);
-        for (int32_t h = 0; h < levels; ++h)
-            for (int32_t i = ht.up_level_off_k[h]; i < ht.up_level_off_k[h + 1]; ++i)
-                hsize[up_order_k[i]] = ht.up_level_off_k[h + 1] - ht.up_level_off_k[h];
-        std::vector<uint8_t> gen(I, 0);
-        int32_t G = 0;
-        for (int32_t d : up_order_k) {
-            int32_t M = -1;
-            for (int32_t e = ht.child_off[d]; e < ht.child_off[d + 1]; ++e)
-                if (is_mat(child_enc_k[e])) M = std::max(M, lv[child_enc_k[e]]);
-            if (M < 0) {
-                lv[d] = 0;
-            } else {
-                bool ok = narrow(d) && hsize[d] <= kUpGroupNodes;
-                int top = 0, g = 0;   // children in launch M, the deepest recomputation below them
-                for (int32_t e = ht.child_off[d]; e < ht.child_off[d + 1] && ok; ++e) {
-                    const int32_t x = child_enc_k[e];
-                    if (is_mat(x) && lv[x] == M) {
-                        ok = recomputable(x) && e - ht.child_off[d] < 2 && gen[x] < kUpGroupDepth;
-                        ++top;
-                        g = std::max(g, (int)gen[x]);
-                    }
-                }
-                ok = ok && (g == 0 || top == 1);   // a chain below: one recomputed child only
-                lv[d] = ok ? M : M + 1;
-                gen[d] = ok ? (uint8_t)(g + 1) : 0;
-                if (ok)
-                    for (int32_t e = ht.child_off[d]; e < ht.child_off[d] + 2 && e < ht.child_off[d + 1]; ++e)
-                        if (is_mat(child_enc_k[e]) && lv[child_enc_k[e]] == M) inl[(size_t)d * 2 + (e - ht.child_off[d])] = child_enc_k[e];
-            }
-            G = std::max(G, lv[d] + 1);
-        }
-        // bucket by (launch, degree class), children-first order kept inside a bucket; in the
-        // out-degree <= 3 class the plain nodes first (binary, neither of the children an S2 / S3
-        // subtree nor recomputed here): one launch of the lean kernel covers them
-        class_off.assign((size_t)G * kDegreeClasses + 1, 0);
-        auto key = [&](int32_t d) { return lv[d] * kDegreeClasses + degree_class(ht.child_off[d + 1] - ht.child_off[d]); };
-        auto sub_shaped_enc = [](int32_t x) { return x >= 0 && (x & kVirtualBit) && ((x >> kShapeShift) & 3); };
-        auto plain = [&](int32_t d) {
-            if (ht.child_off[d + 1] - ht.child_off[d] > 2 || inl[(size_t)d * 2] >= 0 || inl[(size_t)d * 2 + 1] >= 0) return false;
-            for (int32_t e = ht.child_off[d]; e < ht.child_off[d + 1]; ++e)
-                if (sub_shaped_enc(child_enc_k[e])) return false;
-            return true;
-        };
-        for (int32_t d : up_order_k) ++class_off[key(d) + 1];
-        for (size_t k = 0; k + 1 < class_off.size(); ++k) class_off[k + 1] += class_off[k];
-        std::vector<int32_t> order(up_order_k.size()), cur(class_off.begin(), class_off.end() - 1), pos(I, -1);
-        plain_out.assign(G, 0);
-        for (int pass = 0; pass < 2; ++pass)
-            for (int32_t d : up_order_k) {
-                if (plain(d) != (pass == 0)) continue;
-                pos[d] = cur[key(d)]++;
-                order[pos[d]] = d;
-                if (pass == 0) ++plain_out[lv[d]];
-            }
-        level_off.assign(G + 1, 0);
-        for (int32_t l = 0; l <= G; ++l) level_off[l] = class_off[(size_t)l * kDegreeClasses];
-        leafy_out.assign(G, 0);
-        for (int32_t l = 0; l < G; ++l) {
-            bool leafy = true;
-            for (int32_t i = class_off[(size_t)l * kDegreeClasses]; i < class_off[(size_t)l * kDegreeClasses + 1] && leafy; ++i)
-                for (int32_t e = ht.child_off[order[i]]; e < ht.child_off[order[i] + 1]; ++e)
-                    leafy &= !is_mat(child_enc_k[e]);
-            leafy_out[l] = leafy;
-        }
-        std::vector<NodeDesc> desc = make_desc(order, child_enc_k);
-        recomp_out.assign(G, 0);   // launches where some node recomputes a child (the others run the plain kernel)
-        for (size_t k = 0; k < order.size(); ++k) {
-            const int32_t d = order[k];
-            desc[k].pad0 = inl[(size_t)d * 2] >= 0 ? pos[inl[(size_t)d * 2]] : -1;
-            desc[k].pad1 = inl[(size_t)d * 2 + 1] >= 0 ? pos[inl[(size_t)d * 2 + 1]] : -1;
-            if (desc[k].pad0 >= 0 || desc[k].pad1 >= 0) recomp_out[lv[d]] = 1;
-        }
-        return std::make_pair(desc, order);
-    };
-    // (with a sweep plan the grouped Fitch launches stop below its first level: ht.cl.h0)
-    const int32_t all_levels = (int32_t)ht.up_level_off_k.size() - 1;
-    const auto groups_g = make_groups(3, ht.up_level_off_g, ht.up_class_off_g, ht.up_leafy_g, ht.up_recomp_g, ht.up_plain_g,
-                                      ht.cl.band_wg.size() > 1 ? ht.cl.h0 : all_levels);
-    const std::vector<NodeDesc>& up_desc_g = groups_g.first;
-    // up slots: each descriptor's parent item and child slot (the parent's first / second
-    // child) in the same array, for the subtree form's two up orders
-    auto make_pslot = [&](const std::vector<int32_t>& order, const std::vector<NodeDesc>& desc) {
-        std::vector<int32_t> pos(I, -1), ps(order.size(), -1);
-        for (size_t k = 0; k < order.size(); ++k) pos[order[k]] = (int32_t)k;
-        for (size_t k = 0; k < desc.size(); ++k)
-            for (int j = 0; j < 2 && j < desc[k].e1 - desc[k].e0; ++j) {
-                const int32_t x = j == 0 ? desc[k].c0 : desc[k].c1;
-                if (x >= 0 && !(x & kVirtualBit) && pos[x] >= 0) ps[pos[x]] = (int32_t)k * 2 + j;
-            }
-        return ps;
-    };
-    const std::vector<int32_t> pslot_k = make_pslot(up_order_k, up_desc_k), pslot_g = make_pslot(groups_g.second, up_desc_g);
-    // with the sweeps: a level item (either up order) whose parent is swept pushes into the
-    // parent's sweep item's up slot (item cl.upm_base + item); a swept node whose parent is in a
-    // later band likewise (a parent in its own cluster reads its LDS slot instead)
-    std::vector<int32_t> pslot_kc(pslot_k), pslot_gc(pslot_g), cl_pslot(ht.cl.items.size(), -1);
-    ht.cl.upm_base = (int32_t)std::max(up_desc_k.size(), up_desc_g.size());
-    {
-        std::vector<int32_t> pos_k(I, -1), pos_g(I, -1);
-        for (size_t k = 0; k < up_desc_k.size(); ++k) pos_k[up_order_k[k]] = (int32_t)k;
-        for (size_t k = 0; k < groups_g.second.size(); ++k) pos_g[groups_g.second[k]] = (int32_t)k;
-        for (int32_t p = 0; p < I && !ht.cl.item_of.empty(); ++p) {
-            if (ht.cl.item_of[p] < 0) continue;   // swept parents: their first two materialised children
-            const int32_t e0 = ht.child_off[p], e1 = ht.child_off[p + 1];
-            for (int j = 0; j < 2 && e0 + j < e1; ++j) {
-                const int32_t x = child_enc_k[e0 + j];
-                if (x < 0 || (x & kVirtualBit)) continue;
-                const int32_t to = (ht.cl.upm_base + ht.cl.item_of[p]) * 2 + j;
-                if (ht.cl.item_of[x] >= 0) {
-                    cl_pslot[ht.cl.item_of[x]] = ht.cl.slot_of[x] >= 0 ? -1 : to;
-                } else {
-                    if (pos_k[x] >= 0) pslot_kc[pos_k[x]] = to;
-                    if (pos_g[x] >= 0) pslot_gc[pos_g[x]] = to;
-                }
-            }
-        }
-    }
-    ht.up_items_k = (int32_t)up_desc_k.size();
-    ht.up_items_g = (int32_t)up_desc_g.size();
-    // Sankoff: binary recomputed children; its part descriptors are the subtree form's (nodes
-    // above 255 children never group), so pad0 / pad1 here index the grouped array only
-    auto groups_gs = make_groups(2, ht.up_level_off_gs, ht.up_class_off_gs, ht.up_leafy_gs, ht.up_recomp_gs, ht.up_plain_gs,
-                                 all_levels);
-    std::vector<NodeDesc> up_desc_gs = groups_gs.first;
-    const std::vector<int32_t> pslot_gs = make_pslot(groups_gs.second, up_desc_gs);
-    ht.up_items_gs = (int32_t)up_desc_gs.size();
-    // subtree-form pre-order descriptors list only the children the level kernel handles:
-    // S2 / S3 children are tail items (k_tail<.., SUB>); a node left with none gets a
-    // materialised placeholder (c0 = 0, no loads, no records)
-    std::vector<NodeDesc> down_desc_k = with_gp(make_desc(down_order_k, child_enc_k));
-    const std::vector<NodeDesc> down_desc_ks = down_desc_k;   // (PM_OPT_SUB_DOWN: S children kept)
-    for (NodeDesc& x : down_desc_k) {
-        const int32_t deg = x.e1 - x.e0;
-        if (deg > 2) continue;   // S2 / S3 nodes have parents of out-degree <= 2
-        int32_t keep_enc[2], keep_vl[2][4], nk = 0;
-        for (int j = 0; j < deg; ++j) {
-            const int32_t enc = j == 0 ? x.c0 : x.c1;
-            if (enc >= 0 && (enc & kVirtualBit) && ((enc >> kShapeShift) & 3)) continue;
-            keep_enc[nk] = enc;
-            for (int q = 0; q < 4; ++q) keep_vl[nk][q] = j == 0 ? x.vl0[q] : x.vl1[q];
-            ++nk;
-        }
-        if (nk == deg) continue;
-        x.e0 = 0;
-        x.e1 = std::max(nk, 1);
-        x.c0 = nk > 0 ? keep_enc[0] : 0;
-        x.c1 = nk > 1 ? keep_enc[1] : 0;
-        for (int q = 0; q < 4; ++q) {
-            x.vl0[q] = nk > 0 ? keep_vl[0][q] : -1;
-            x.vl1[q] = nk > 1 ? keep_vl[1][q] : -1;
-        }
-    }
-    // the pre-order over the sweeps' clusters (every level swept only)
-    ht.cl.down = plan_cluster_down(ht, down_order_k, down_desc_k, child_enc_k, ht.cl);
-    phase_add("cluster.down", ht.cl.down ? 1.0 : 0.0);
-    auto make_tail = [&](const std::vector<int32_t>& order, const std::vector<int32_t>& enc) {
-        std::vector<TailDesc> tail;
-        for (int32_t d : order)
-            for (int32_t e = ht.child_off[d] + 2; e < ht.child_off[d + 1]; ++e) {
-                const int32_t x = enc[e];
-                if (x >= 0 && !(x & kVirtualBit)) continue;   // materialised child: its own wave
-                TailDesc t{};
-                t.parent = d;
-                t.enc = x;
-                t.ix = t.iy = -1;
-                for (int j = 0; j < 4; ++j) t.vl[j] = x >= 0 ? vleaf[(size_t)(x & kDenseMask) * 4 + j] : -1;
-                t.id[0] = x < 0 ? ht.leaf_id[-x - 1] : ht.internal_id[x & kDenseMask];
-                for (int j = 0; j < 4; ++j) t.id[1 + j] = t.vl[j] >= 0 ? ht.leaf_id[t.vl[j]] : -1;
-                tail.push_back(t);
-            }
-        return tail;
-    };
-    upload_phase("descriptors");
-    std::vector<TailDesc> tail_desc = make_tail(down_order, ht.child_enc);
-    std::vector<TailDesc> tail_desc_v = make_tail(down_order_v, child_enc_v);
-    ht.num_tail = (int32_t)tail_desc.size();
-    ht.num_tail_v = (int32_t)tail_desc_v.size();
-    // subtree form: every S2 / S3 node, in dense order (item k = dense index sbase + k), then
-    // the leaf-parent form's items
-    std::vector<TailDesc> tail_desc_k;
-    ht.sbase = -1;
-    for (int32_t d = 0; d < I; ++d) {
-        if (!sshape[d]) continue;
-        if (ht.sbase < 0) ht.sbase = d;
-        TailDesc t{};
-        t.parent = parent_dense[d];
-        t.enc = (d | kVirtualBit) | (sshape[d] << kShapeShift);
-        for (int j = 0; j < 4; ++j) t.vl[j] = vleaf[(size_t)d * 4 + j];
-        t.ix = ht.internal_id[vinner[(size_t)d * 2]];
-        t.iy = vinner[(size_t)d * 2 + 1] >= 0 ? ht.internal_id[vinner[(size_t)d * 2 + 1]] : -1;
-        t.id[0] = ht.internal_id[d];
-        for (int j = 0; j < 4; ++j) t.id[1 + j] = t.vl[j] >= 0 ? ht.leaf_id[t.vl[j]] : -1;
-        tail_desc_k.push_back(t);
-    }
-    ht.num_tail_s = (int32_t)tail_desc_k.size();
-    for (int32_t k = 0; k < ht.num_tail_s; ++k)
-        if (ht.sbase + k >= I || !sshape[ht.sbase + k]) return fail(c, PM_ERR_STATE, "S2 / S3 nodes not one dense range");
-    // tail items by their parent's pre-order level (the subtree form's levels are the leaf-
-    // parent form's, S2 / S3 nodes removed): neighbouring waves read neighbouring parents
-    {
-        auto by_level = [&](std::vector<TailDesc>& tail, const std::vector<int32_t>& order,
-                            const std::vector<int32_t>& offs) {
-            std::vector<int32_t> lvl_of(I, 0);
-            for (size_t l = 0; l + 1 < offs.size(); ++l)
-                for (int32_t i = offs[l]; i < offs[l + 1]; ++i) lvl_of[order[i]] = (int32_t)l;
-            std::stable_sort(tail.begin(), tail.end(),
-                             [&](const TailDesc& x, const TailDesc& y) { return lvl_of[x.parent] < lvl_of[y.parent]; });
-        };
-        by_level(tail_desc, down_order, ht.down_level_off);
-        by_level(tail_desc_v, down_order_v, ht.down_level_off_v);
-    }
-    tail_desc_k.insert(tail_desc_k.end(), tail_desc_v.begin(), tail_desc_v.end());
-    ht.num_tail_k = (int32_t)tail_desc_k.size();
-
-    // Sankoff parts: nodes of out-degree > 255, children cut into kPartChildren-wide parts
-    std::vector<PartDesc> part_desc[4];
-    for (int v = 0; v < 4; ++v) {
-        const std::vector<NodeDesc>& ud = v == 3 ? up_desc_gs : v == 2 ? up_desc_k : v ? up_desc_v : up_desc;
-        std::vector<int32_t>& po = v == 3 ? ht.part_off_gs : v == 2 ? ht.part_off_k : v ? ht.part_off_v : ht.part_off;
-        po.assign(ud.size() + 1, 0);
-        ht.up_degree[v].assign(ud.size(), 0);
-        for (size_t k = 0; k < ud.size(); ++k) {
-            const int32_t deg = ud[k].e1 - ud[k].e0;
-            ht.up_degree[v][k] = deg;
-            const int32_t np = deg > 255 ? (deg + kPartChildren - 1) / kPartChildren : 0;
-            for (int32_t j = 0; j < np; ++j) part_desc[v].push_back(PartDesc{(int32_t)k, j, po[k] + j, 0});
-            po[k + 1] = po[k] + np;
-        }
-    }
-    // pad0 = the first part (Sankoff up descriptors; the Fitch level kernels do not read it)
-    std::vector<NodeDesc> up_desc_p = up_desc, up_desc_vp = up_desc_v, up_desc_kp = up_desc_k;
-    for (size_t k = 0; k < up_desc_p.size(); ++k) up_desc_p[k].pad0 = ht.part_off[k];
-    for (size_t k = 0; k < up_desc_vp.size(); ++k) up_desc_vp[k].pad0 = ht.part_off_v[k];
-    for (size_t k = 0; k < up_desc_kp.size(); ++k) up_desc_kp[k].pad0 = ht.part_off_k[k];
-    for (size_t k = 0; k < up_desc_gs.size(); ++k)   // (grouped nodes have out-degree <= 3: pad0 / pad1 stay theirs)
-        if (up_desc_gs[k].e1 - up_desc_gs[k].e0 > 255) up_desc_gs[k].pad0 = ht.part_off_gs[k];
-    upload_phase("parts");
-    std::vector<int32_t> lvl;
-    {
-        const std::vector<int32_t>* up[5] = {&ht.up_class_off, &ht.up_class_off_v, &ht.up_class_off_k, &ht.up_class_off_g,
-                                             &ht.up_class_off_gs};
-        const std::vector<int32_t>* dn[3] = {&ht.down_level_off, &ht.down_level_off_v, &ht.down_level_off_k};
-        for (int f = 0; f < 5; ++f) {
-            ht.lvl_up[f] = (int64_t)lvl.size();
-            lvl.insert(lvl.end(), up[f]->begin(), up[f]->end());
-            if (f >= 3) continue;
-            ht.lvl_down[f] = (int64_t)lvl.size();
-            lvl.insert(lvl.end(), dn[f]->begin(), dn[f]->end());
-        }
-        ht.lvl_base_k = (int64_t)lvl.size();
-        lvl.insert(lvl.end(), ht.down_dense_base_k.begin(), ht.down_dense_base_k.end());
-    }
-
+    // the host plan (pm_plan.cpp); a tree it refuses leaves the context's tree as it was
+    TreePlan p;
+    std::string err;
+    if (const int rc = plan_tree(*t, c->cluster_max_level, c->cluster_chain, p, err)) return fail(c, rc, err);
+    PhaseClock clock;
     free_work(c);
     free_columns(c);
     free_tree(c->dt);
     DevTree dt;
-    dt.num_internal = I;
-    dt.num_leaves = L;
-    dt.root_dense = ht.dense_of[t->root];
-    hipError_t e;
-    size_t tree_bytes = 0;   // (pm_memory_footprint)
-    auto up = [&](auto** dst, const auto& v) {
-        tree_bytes += sizeof(v[0]) * v.size();
-        return upload(dst, v, c->stream);
-    };
-    if ((e = up(&dt.child_off, ht.child_off)) != hipSuccess ||
-        (e = up(&dt.child_enc, ht.child_enc)) != hipSuccess ||
-        (e = up(&dt.parent_dense, parent_dense)) != hipSuccess ||
-        (e = up(&dt.internal_id, ht.internal_id)) != hipSuccess ||
-        (e = up(&dt.leaf_id, ht.leaf_id)) != hipSuccess ||
-        (e = up(&dt.up_order, up_order)) != hipSuccess ||
-        (e = up(&dt.down_order, down_order)) != hipSuccess ||
-        (e = up(&dt.leaf_parent, leaf_parent)) != hipSuccess ||
-        (e = up(&dt.leaf_down, leaf_down)) != hipSuccess ||
-        (e = up(&dt.child_enc_v, child_enc_v)) != hipSuccess ||
-        (e = up(&dt.up_order_v, up_order_v)) != hipSuccess ||
-        (e = up(&dt.down_order_v, down_order_v)) != hipSuccess ||
-        (e = up(&dt.down_desc, down_desc)) != hipSuccess ||
-        (e = up(&dt.up_desc, up_desc_p)) != hipSuccess ||
-        (e = up(&dt.up_desc_v, up_desc_vp)) != hipSuccess ||
-        (e = up(&dt.down_desc_v, down_desc_v)) != hipSuccess ||
-        (e = up(&dt.vleaf, vleaf)) != hipSuccess ||
-        (e = up(&dt.tail_desc, tail_desc)) != hipSuccess ||
-        (e = up(&dt.tail_desc_v, tail_desc_v)) != hipSuccess ||
-        (e = up(&dt.part_desc, part_desc[0])) != hipSuccess ||
-        (e = up(&dt.part_desc_v, part_desc[1])) != hipSuccess ||
-        (e = up(&dt.part_desc_k, part_desc[2])) != hipSuccess ||
-        (e = up(&dt.part_desc_gs, part_desc[3])) != hipSuccess ||
-        (e = up(&dt.child_enc_k, child_enc_k)) != hipSuccess ||
-        (e = up(&dt.up_desc_k, up_desc_kp)) != hipSuccess ||
-        (e = up(&dt.up_desc_g, up_desc_g)) != hipSuccess ||
-        (e = up(&dt.up_desc_gs, up_desc_gs)) != hipSuccess ||
-        (e = up(&dt.down_desc_k, down_desc_k)) != hipSuccess ||
-        (e = up(&dt.down_desc_ks, down_desc_ks)) != hipSuccess ||
-        (e = up(&dt.pslot_k, pslot_k)) != hipSuccess ||
-        (e = up(&dt.pslot_g, pslot_g)) != hipSuccess ||
-        (e = up(&dt.pslot_gs, pslot_gs)) != hipSuccess ||
-        (e = up(&dt.vinner, vinner)) != hipSuccess ||
-        (e = up(&dt.tail_desc_k, tail_desc_k)) != hipSuccess ||
-        (e = up(&dt.lvl, lvl)) != hipSuccess ||
-        (e = up(&dt.cl_items, ht.cl.items)) != hipSuccess ||
-        (e = up(&dt.cl_down_items, ht.cl.down_items)) != hipSuccess ||
-        (e = up(&dt.cl_wg_off, ht.cl.wg_off)) != hipSuccess ||
-        (e = up(&dt.cl_slot_of, ht.cl.slot_of)) != hipSuccess ||
-        (e = up(&dt.pslot_kc, pslot_kc)) != hipSuccess ||
-        (e = up(&dt.pslot_gc, pslot_gc)) != hipSuccess ||
-        (e = up(&dt.cl_pslot, cl_pslot)) != hipSuccess) {
-        free_tree(dt);
-        return hip_fail(c, e, "tree upload");
-    }
-    for (const NodeDesc& x : ht.cl.items) ht.cl.max_degree = std::max(ht.cl.max_degree, x.e1 - x.e0);
-    ht.cl.items.clear();   // (device only)
-    ht.cl.items.shrink_to_fit();
-    ht.cl.down_items.clear();
-    ht.cl.down_items.shrink_to_fit();
-    ht.cl.item_of.clear();
-    ht.cl.item_of.shrink_to_fit();
+    size_t tree_bytes = 0;
+    const hipError_t e = upload_tree(p, c->stream, dt, tree_bytes);
+    if (e != hipSuccess) return hip_fail(c, e, "tree upload");
+    ClusterPlan& cl = p.ht.cl;
+    for (const NodeDesc& x : cl.items) cl.max_degree = std::max(cl.max_degree, x.e1 - x.e0);
+    cl.items.clear();   // (device only)
+    cl.items.shrink_to_fit();
+    cl.down_items.clear();
+    cl.down_items.shrink_to_fit();
+    cl.item_of.clear();
+    cl.item_of.shrink_to_fit();
     c->dt = dt;
     c->tree_bytes = tree_bytes;
-    c->ht = std::move(ht);
+    c->ht = std::move(p.ht);
     c->max_degree = 0;
-    for (int32_t d = 0; d < I; ++d) c->max_degree = std::max(c->max_degree, c->ht.child_off[d + 1] - c->ht.child_off[d]);
+    for (int32_t d = 0; d < dt.num_internal; ++d) c->max_degree = std::max(c->max_degree, c->ht.child_off[d + 1] - c->ht.child_off[d]);
     c->has_tree = true;
-    upload_phase("device upload");
+    tree_phase(clock, "device upload");
     return PM_OK;
 }
 
@@ -1631,108 +960,6 @@ int pm_consensus_fetch(pm_ctx* c, int64_t s0, int64_t ns, uint8_t* out) {
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     dev_free(d);
     return e == hipSuccess ? PM_OK : hip_fail(c, e, "consensus fetch");
-}
-
-int pm_synth_tree_random_join(int64_t leaves, uint64_t seed, int32_t* child_offsets, int32_t* child_index,
-                              int32_t* root) {
-    // SURVEY.md §8d family T1: repeatedly join two uniformly chosen pool items.
-    if (leaves < 2 || leaves > (int64_t)1 << 30 || !child_offsets || !child_index || !root) return PM_ERR_ARG;
-    std::mt19937_64 rng(seed);
-    std::vector<int32_t> pool(leaves);
-    std::iota(pool.begin(), pool.end(), 0);
-    const int64_t N = 2 * leaves - 1;
-    for (int64_t i = 0; i <= leaves; ++i) child_offsets[i] = 0;
-    int32_t next = (int32_t)leaves;
-    int64_t e = 0;
-    while (pool.size() > 1) {
-        size_t m = pool.size();
-        size_t a = rng() % m;
-        std::swap(pool[a], pool[m - 1]);
-        const int32_t x = pool[m - 1];
-        pool.pop_back();
-        --m;
-        size_t b = rng() % m;
-        std::swap(pool[b], pool[m - 1]);
-        const int32_t y = pool[m - 1];
-        pool.pop_back();
-        child_index[e++] = x;
-        child_index[e++] = y;
-        child_offsets[next + 1] = (int32_t)e;
-        pool.push_back(next++);
-    }
-    (void)N;
-    *root = pool[0];
-    return PM_OK;
-}
-
-int pm_synth_tree_sars_like(int64_t leaves, uint64_t seed, int32_t* child_offsets, int32_t* child_index,
-                            int32_t* root, int64_t* num_nodes) {
-    // SURVEY.md §8d family T2: ladderised sequential insertion -- leaf i splits the pendant
-    // edge of leaf i-1 with p = 0.9, else of a uniform earlier leaf -- then 10 % of the
-    // internal nodes are merged away (edge contraction) into polytomies of 3-64 children.
-    if (leaves < 2 || leaves > (int64_t)1 << 29 || !child_offsets || !child_index || !root || !num_nodes)
-        return PM_ERR_ARG;
-    std::mt19937_64 rng(seed);
-    auto uniform = [&](uint64_t n) { return (uint64_t)((unsigned __int128)rng() * n >> 64); };
-    auto coin = [&](double p) { return (double)(rng() >> 11) * 0x1.0p-53 < p; };
-    const int64_t L = leaves, N0 = 2 * leaves - 1;
-    std::vector<int32_t> par(N0, -1);
-    std::vector<std::vector<int32_t>> kids(N0);
-    int32_t next = (int32_t)L;
-    const int32_t r = next++;
-    kids[r] = {0, 1};
-    par[0] = par[1] = r;
-    for (int64_t i = 2; i < L; ++i) {
-        const int32_t t = coin(0.9) ? (int32_t)(i - 1) : (int32_t)uniform((uint64_t)i);
-        const int32_t q = par[t], v = next++;
-        for (int32_t& k : kids[q])
-            if (k == t) k = v;
-        par[v] = q;
-        kids[v] = {t, (int32_t)i};
-        par[t] = par[i] = v;
-    }
-    // polytomies: visit internal non-root nodes in random order; a visited node absorbs
-    // internal children (its own kids first) until it has k ~ U[3,64] children, never more
-    // than 64, until 10 % of the internal nodes are gone
-    std::vector<int32_t> perm;
-    for (int32_t v = (int32_t)L + 1; v < next; ++v) perm.push_back(v);
-    for (size_t i = perm.size(); i > 1; --i) std::swap(perm[i - 1], perm[uniform(i)]);
-    std::vector<uint8_t> dead(N0, 0);
-    int64_t budget = (int64_t)(0.1 * (double)(next - L));
-    for (int32_t v : perm) {
-        if (budget <= 0) break;
-        if (dead[v]) continue;
-        const size_t k = 3 + (size_t)uniform(62);
-        size_t scan = 0;
-        while (kids[v].size() < k && budget > 0 && scan < kids[v].size()) {
-            const int32_t c = kids[v][scan];
-            if (c < L || kids[v].size() - 1 + kids[c].size() > 64) {
-                ++scan;
-                continue;
-            }
-            std::vector<int32_t> g = std::move(kids[c]);
-            kids[v].erase(kids[v].begin() + scan);
-            kids[v].insert(kids[v].begin() + scan, g.begin(), g.end());
-            for (int32_t x : g) par[x] = v;
-            dead[c] = 1;
-            --budget;
-        }
-    }
-    // compact ids: leaves keep [0, L), surviving internal nodes follow in creation order
-    std::vector<int32_t> id(N0, -1);
-    int32_t n = 0;
-    for (int32_t v = 0; v < next; ++v)
-        if (!dead[v]) id[v] = n++;
-    int64_t e = 0;
-    child_offsets[0] = 0;
-    for (int32_t v = 0; v < next; ++v) {
-        if (dead[v]) continue;
-        for (int32_t c : kids[v]) child_index[e++] = id[c];
-        child_offsets[id[v] + 1] = (int32_t)e;
-    }
-    *root = id[r];
-    *num_nodes = n;
-    return PM_OK;
 }
 
 }  // extern "C"

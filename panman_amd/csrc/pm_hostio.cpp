@@ -1,7 +1,7 @@
-// pm_hostio.cpp -- host-side plumbing around the kernels: the phase log every driver writes
-// its host / device phase times into (pm_phase_report), large device-to-host downloads
+// pm_hostio.cpp -- host-side plumbing around the kernels: large device-to-host downloads
 // through pinned staging buffers drained by a pool of host threads (the FASTA text), and
-// the grow-only device buffers a context keeps between calls.
+// the grow-only device buffers a context keeps between calls.  (The phase log and the host
+// worker threads need no GPU: pm_hostpar.cpp, pm_pool.h.)
 //
 // Why the download pipeline: printFASTAUltraFast's output at config C5 is ~5 GB of text.
 // One pageable hipMemcpy of it runs single-threaded through the runtime's own staging and
@@ -28,128 +28,9 @@
 #include <vector>
 
 #include "pm_internal.h"
+#include "pm_pool.h"
 
 namespace pm {
-
-// ---- phase log ---------------------------------------------------------------------------
-namespace {
-std::mutex g_phase_mu;
-std::vector<std::pair<std::string, double>> g_phases;
-constexpr size_t kMaxPhases = 4096;
-}  // namespace
-
-void phase_add(const std::string& name, double seconds) {
-    std::lock_guard<std::mutex> lock(g_phase_mu);
-    if (g_phases.size() < kMaxPhases) g_phases.emplace_back(name, seconds);
-}
-
-PhaseClock::PhaseClock() : t(std::chrono::steady_clock::now()) {}
-
-double PhaseClock::lap(const char* name) {
-    const auto now = std::chrono::steady_clock::now();
-    const double s = std::chrono::duration<double>(now - t).count();
-    phase_add(name, s);
-    t = now;
-    return s;
-}
-
-int host_threads() {
-    if (const char* e = std::getenv("PM_HOST_THREADS")) {
-        const int v = std::atoi(e);
-        if (v >= 1 && v <= 256) return v;
-    }
-    const unsigned hc = std::thread::hardware_concurrency();
-    return (int)std::max(1u, std::min(16u, hc ? hc : 1u));
-}
-
-// ---- a small fork-join pool: run(n, fn) calls fn(0..n-1) on the workers and the caller ----
-namespace {
-class Pool {
-  public:
-    explicit Pool(int threads) {
-        for (int i = 1; i < threads; ++i) workers_.emplace_back([this]() { loop(); });
-    }
-    ~Pool() {
-        {
-            std::lock_guard<std::mutex> lock(mu_);
-            stop_ = true;
-        }
-        cv_.notify_all();
-        for (auto& t : workers_) t.join();
-    }
-    int size() const { return (int)workers_.size() + 1; }
-    // One generation at a time: run() publishes (job, tasks) only when no worker is inside
-    // work(), and returns only when every task is done and every worker has left work(), so a
-    // worker never mixes one generation's job with another's counter.  Workers take their
-    // (job, tasks) snapshot under the lock.
-    template <class F>
-    void run(int tasks, F&& fn) {
-        std::function<void(int)> f(std::forward<F>(fn));
-        {
-            std::unique_lock<std::mutex> lock(mu_);
-            done_.wait(lock, [this]() { return active_ == 0; });
-            job_ = &f;
-            tasks_ = tasks;
-            next_.store(0);
-            pending_ = tasks;
-            ++gen_;
-        }
-        cv_.notify_all();
-        work(&f, tasks);
-        std::unique_lock<std::mutex> lock(mu_);
-        done_.wait(lock, [this]() { return pending_ == 0 && active_ == 0; });
-        job_ = nullptr;
-    }
-
-  private:
-    void work(std::function<void(int)>* job, int tasks) {
-        for (int i = next_++; i < tasks; i = next_++) {
-            (*job)(i);
-            std::lock_guard<std::mutex> lock(mu_);
-            if (--pending_ == 0) done_.notify_all();
-        }
-    }
-    void loop() {
-        uint64_t seen = 0;
-        for (;;) {
-            std::function<void(int)>* job = nullptr;
-            int tasks = 0;
-            {
-                std::unique_lock<std::mutex> lock(mu_);
-                cv_.wait(lock, [&]() { return stop_ || gen_ != seen; });
-                if (stop_) return;
-                seen = gen_;
-                if (!job_) continue;   // that generation has finished already
-                job = job_;
-                tasks = tasks_;
-                ++active_;
-            }
-            work(job, tasks);
-            std::lock_guard<std::mutex> lock(mu_);
-            if (--active_ == 0) done_.notify_all();
-        }
-    }
-    std::vector<std::thread> workers_;
-    std::mutex mu_;
-    std::condition_variable cv_, done_;
-    std::function<void(int)>* job_ = nullptr;
-    int tasks_ = 0, pending_ = 0, active_ = 0;
-    std::atomic<int> next_{0};
-    uint64_t gen_ = 0;
-    bool stop_ = false;
-};
-}  // namespace
-
-void host_parallel_for(int tasks, const std::function<void(int)>& fn) {
-    if (tasks <= 0) return;
-    const int t = std::min(tasks, host_threads());
-    if (t <= 1) {
-        for (int i = 0; i < tasks; ++i) fn(i);
-        return;
-    }
-    Pool pool(t);
-    pool.run(tasks, fn);
-}
 
 // ---- large downloads ---------------------------------------------------------------------
 constexpr size_t kStageChunk = (size_t)64 << 20;   // bytes per pinned slot
@@ -319,34 +200,6 @@ hipError_t grow_device(void** buf, size_t* cap, size_t need) {
 }
 
 }  // namespace pm
-
-extern "C" {
-
-void pm_phase_reset(void) {
-    std::lock_guard<std::mutex> lock(pm::g_phase_mu);
-    pm::g_phases.clear();
-}
-
-int64_t pm_phase_report(char* buf, int64_t len) {
-    std::string s;
-    {
-        std::lock_guard<std::mutex> lock(pm::g_phase_mu);
-        char line[64];
-        for (auto& p : pm::g_phases) {
-            std::snprintf(line, sizeof line, "\t%.6f\n", p.second);
-            s += p.first;
-            s += line;
-        }
-    }
-    if (buf && len > 0) {
-        const size_t n = std::min<size_t>(s.size(), (size_t)len - 1);
-        std::memcpy(buf, s.data(), n);
-        buf[n] = 0;
-    }
-    return (int64_t)s.size() + 1;
-}
-
-}  // extern "C"
 
 extern "C" {
 

@@ -1,7 +1,7 @@
 """Deterministic edge-case trees and mixed-class columns (host only, numpy).
 
 Every generator returns (off, idx, root) in the CSR form of _trees.random_tree, leaf ids first.
-The shapes are built around the engine's planner and launcher limits (pm_host.cpp,
+The shapes are built around the engine's planner and launcher limits (pm_plan.cpp,
 pm_cluster.cpp): out-degree classes <= 3 | 4-15 | 16-255 | > 255, the sweeps' 64 nodes per
 cluster, 32 heights per band and 4 LDS slots, and the compressed records' three word classes
 (consensus, simple, complex)."""

@@ -63,7 +63,7 @@ def _heights(off, idx, root):
 
 def _materialised(off, idx, root):
     """Internal nodes the subtree form keeps: not a one- or two-leaf leaf-parent, not an S2 / S3
-    node under a parent of out-degree <= 2 (pm_host.cpp: virtual_id, sshape_id)."""
+    node under a parent of out-degree <= 2 (pm_plan.cpp: leaf_parent_like, sshape_of)."""
     n = off.shape[0] - 1
     parent = np.full(n, -1, np.int64)
     for v in range(n):
