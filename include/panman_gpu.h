@@ -170,6 +170,10 @@ int pm_set_stream(pm_ctx* ctx, void* hip_stream);
  *   PM_OPT_AA_BATCH_BYTES (default 1 GiB, at least 4096): pm_aa / pm_aa_fd build the codon tables and
  *                  the lines of a batch of nodes in at most this much device memory (always at least
  *                  one node) and stream the text batch by batch.  The text does not depend on it.
+ *   PM_OPT_MUTATIONS_BATCH_BYTES (default 1 GiB, at least 4096): pm_print_mutations / pm_print_mutations_fd
+ *                  cut the nodes in id order into batches by the bytes of their entry records plus the
+ *                  worst-case text (a node above the limit runs alone) and stream the text batch by
+ *                  batch.  The text does not depend on it.
  * (Option ids 1, 4, 5 and 11 -- subtree-region, heavy-path-chain and level-band schedules,
  * tail records overlapped with the pre-order levels -- were measured slower than, or no
  * faster than, the level kernels on MI355X and removed.) */
@@ -193,6 +197,7 @@ int pm_set_stream(pm_ctx* ctx, void* hip_stream);
 #define PM_OPT_GFA_IN_BATCH_SITES 23
 #define PM_OPT_SUBNET_BATCH_ENTRIES 24
 #define PM_OPT_AA_BATCH_BYTES 25
+#define PM_OPT_MUTATIONS_BATCH_BYTES 26
 int pm_set_option(pm_ctx* ctx, int option, int64_t value);
 /* Accumulate per-kernel-class device time with HIP events (see pm_kernel_times). */
 int pm_set_profiling(pm_ctx* ctx, int enable);
@@ -597,6 +602,59 @@ int pm_aa(pm_ctx* ctx, const pm_panmat* panmat, int64_t start, int64_t end, char
           int64_t* ref_codons, int64_t* unlocated);
 int pm_aa_fd(pm_ctx* ctx, const pm_panmat* panmat, int64_t start, int64_t end, int fd, int64_t* length,
              int64_t* ref_codons, int64_t* unlocated);
+/* Drop-in for Tree::printMutationsNew(std::ostream&) (src/panman.cpp:3699-4057; the --printMutations
+ * command without --input-file, src/panmanUtils.cpp:1008-1071): per node of the tree, which bases
+ * changed against its parent, in the root's coordinates.  Rotation, sequence inversion and circular
+ * offset play no part.  A node's sequence is getSequenceFromReference(rotate = false) (src/panman.cpp:
+ * 4676-4972): all block mutations of its path first, then the nucleotide mutations of the blocks it
+ * holds at the end of the path only, so a block it does not hold keeps its consensus and its empty
+ * gap slots.  A cell is (block, position 0..n_b, slot), slot -1 the main character, n_b the 'x'
+ * sentinel.
+ *   root map      (:3725-3806) the root's blocks by id; a held forward block is walked per position
+ *                 (slots ascending, then the main character), a held reverse block with positions
+ *                 descending (the main character, then the slots descending).  coord(cell) = the root
+ *                 characters that are neither '-' nor 'x' walked before the cell; gap(cell) = the
+ *                 root's own character there is '-' or 'x'.  In a block the root does not hold every
+ *                 cell gets the running count unchanged and gap = false.
+ *   seqChar(u)    (:3810-3849) a slot: u's character, 'x' as '-', with no held test.  A main character
+ *                 of a block whose strand flag is forward: u's character if it is neither '-' nor 'x'
+ *                 and u holds the block, else '-'.  Of a block whose flag is reverse: the ROOT's
+ *                 stored main character at that position, unnormalised ('x' at the sentinel), if u's
+ *                 is neither '-' nor 'x', else '-' (a quirk of :3835, kept).
+ *   entries       only the node's own nucleotide mutations, in list order (:3901); the root has none.
+ *                 held(u, b) starts from the root's held blocks; an insertion anywhere on the path
+ *                 sets it, a deletion that is no inversion clears it (:3874-3899).  `old` is always
+ *                 the PARENT's seqChar, `new` the element's code as a character; element j's cell is
+ *                 (b, pos, gap + j) when gap != -1, else (b, pos + j, -1).
+ *                   NS (type 0), per element: nothing unless held(u, b); nothing when old is '-' or
+ *                     'x'; otherwise an S entry.
+ *                   NI (2): an I entry per element, no held test.
+ *                   ND (1): a D entry per element with old as read (it may be '-'), no held test.
+ *                   NSNPS (3): one S entry when held, also over an old '-' or 'x' (the reference
+ *                     prints a notice); these are counted in `*odd_substitutions`.
+ *                   NSNPI (4), NSNPD (5) and above: no entry at all (:3913, :3987), so single-base
+ *                     insertions and deletions are missing from the reference's output and from this.
+ * Text (:4025-4055), per node three lines, entries in list order within each, g present iff gap(cell):
+ *   "Substitutions:\t<name>\t" { " > " [g] old coord+1 new } "\n"
+ *   "Insertions:\t<name>\t"    { " > " [g] coord+1 new } "\n"
+ *   "Deletions:\t<name>\t"     { " > " [g] coord+1 old } "\n"
+ * Deviations: nodes are printed in node-id order (the reference iterates a
+ * tbb::concurrent_unordered_map); the stdout notices ("INVERTED BLOCK FOUND", "INVERSION FOUND", "NOT
+ * ACTUALLY A SUBSTITUTION") are not printed; a nucleotide mutation on a secondary block:
+ * PM_ERR_UNSUPPORTED (as pm_maf / pm_aa); a node that ends its path with a block not held but flagged
+ * reverse (an inversion of a block it does not hold): PM_ERR_UNSUPPORTED, found on the host before
+ * any text is produced; a mutation (types 0 to 5) whose cell does not exist: PM_ERR_ARG, and on an id
+ * that holds no block PM_ERR_UNSUPPORTED, both from the replay (the reference would default-insert
+ * into its maps, or skip the id); rows of 2^31 - 64 columns and more: PM_ERR_UNSUPPORTED.
+ * The rows of all nodes come from one replay of the derived PanMAT of pm_aa.  The root's coordinates
+ * (a count over all columns), the expansion of the mutation lists into one entry per base, the
+ * parent-row lookups, the line lengths and the text are computed on the GPU (profiling class 3),
+ * batch by batch of nodes (PM_OPT_MUTATIONS_BATCH_BYTES), the text streamed through the pinned
+ * download slots.  Phase log: mutations.*.  Memory: the replayed rows are nodes x columns bytes.
+ * `*text` is malloc'd (release with pm_free); pm_print_mutations_fd writes to `fd` instead (`length`,
+ * `odd_substitutions` nullable).  A failed write: PM_ERR_ARG (errno kept), as pm_fasta_fd. */
+int pm_print_mutations(pm_ctx* ctx, const pm_panmat* panmat, char** text, int64_t* length, int64_t* odd_substitutions);
+int pm_print_mutations_fd(pm_ctx* ctx, const pm_panmat* panmat, int fd, int64_t* length, int64_t* odd_substitutions);
 /* Canonical aligned columns per leaf of the prepared PanMAT (gap slots before each main
  * position, block sentinels included) and the number of leaves. */
 int pm_replay_shape(pm_ctx* ctx, int64_t* leaves, int64_t* columns, int64_t* edits);

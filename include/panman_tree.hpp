@@ -177,6 +177,18 @@ class Tree {
         pm_free(text);
     }
 
+    // Tree::printMutationsNew(fout) (src/panman.cpp:3699-4057): three lines per node, nodes in id
+    // order; the reference's stdout notices are not printed (pm_print_mutations).
+    void printMutationsNew(std::ostream& fout) const {
+        detail::Ctx ctx(device_);
+        pm_panmat v = view();
+        char* text = nullptr;
+        int64_t len = 0;
+        ctx.check(pm_print_mutations(ctx.c, &v, &text, &len, nullptr), "pm_print_mutations");
+        fout.write(text, (std::streamsize)len);
+        pm_free(text);
+    }
+
     // Tree::printSummary(out) (src/summary.cpp:257-273); the block lines go to std::cout as
     // getBlockMutationsParallel prints them (:203-250).
     void printSummary(std::ostream& out) const {

@@ -58,6 +58,7 @@ const Spec kSpecs[] = {
     {"subnet", 'b', false, "Extract subnet of given PanMAN to a new PanMAN file based on the list of nodes provided in the input-file"},
     {"input-file", 'i', true, "Path to the input file, required for --subnet (one line per tree: treeID id id ...)"},
     {"reroot", 'r', false, "Reroot a PanMAT in a PanMAN based on the input sequence id (--reference)"},
+    {"printMutations", 'p', false, "Print mutations from root to each node (every node of the tree given by --treeID, default 0)"},
     {"aa-translation", 0, false, "Extract amino acid translations in TSV file (needs --treeID, --start and --end)"},
     {"start", 'x', true, "Start coordinate of protein translation"},
     {"end", 'y', true, "End coordinate of protein translation"},
@@ -75,7 +76,7 @@ const Spec kSpecs[] = {
 // Reference commands outside the accelerated path: recognised so the error is explicit.
 const char* const kOther[] = {"impute", "create-network", "printTips",
                               "vcf", "annotate",
-                              "extended-newick", "printMutations", "acr", "index",
+                              "extended-newick", "acr", "index",
                               "toUsher"};
 
 void usage(std::ostream& os) {
@@ -388,6 +389,22 @@ int one_tree_text(const Options& o, const pm_panman* file, int device, const cha
     return status;
 }
 
+// -I in.panman --printMutations [--treeID k] [-o out] (src/panmanUtils.cpp:1008-1071):
+// Tree::printMutationsNew(std::ostream&) of one tree to stdout or ./info/<out>.mutations
+// (pm_print_mutations_fd).  The forms with a node list (--input-file) or a reference string
+// (--refFile) are not built.
+int print_mutations_fd(pm_ctx* ctx, const pm_panmat* view, int fd, int64_t* length) {
+    return pm_print_mutations_fd(ctx, view, fd, length, nullptr);
+}
+
+int print_mutations(const Options& o, const pm_panman* file, int device) {
+    if (o.has("input-file")) {
+        print_error("--printMutations with --input-file: the node-list and --refFile forms are not built");
+        return 1;
+    }
+    return one_tree_text(o, file, device, ".mutations", print_mutations_fd, "\nMutation extract execution time: ");
+}
+
 // -I in.panman --aa-translation --treeID k -x start -y end [-o out] (src/panmanUtils.cpp:895-938):
 // Tree::extractAminoAcidTranslations of one tree to stdout or ./info/<out>.tsv (pm_aa / pm_aa_fd).
 // stdout receives the reference's "<n> <n> <n>" line (the sizes of the root's three codon lists)
@@ -637,6 +654,11 @@ int from_panman(const Options& o, const std::vector<int>& devices) {
     }
     if (o.has("gfa")) {
         status = one_tree_text(o, file, device, ".gfa", pm_gfa_fd, "GFA generation time: ");
+        pm_panman_free(file);
+        return status;
+    }
+    if (o.has("printMutations")) {
+        status = print_mutations(o, file, device);
         pm_panman_free(file);
         return status;
     }

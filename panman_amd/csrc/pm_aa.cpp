@@ -15,52 +15,11 @@
 #include <vector>
 
 #include "pm_dev.h"
+#include "pm_every_node.h"
 #include "pm_replay.h"
 
 namespace pm {
 namespace {
-
-// `p` with a childless, mutation-free child under every internal node (ids num_nodes, ... in
-// the order of their parents); its arrays live in the object.
-struct EveryNodeATip {
-    pm_panmat q;
-    std::vector<int32_t> child_offsets, child_index, tip_of;   // tip_of[v]: the leaf whose row is v's
-    std::vector<int64_t> block_mut_offsets, nuc_mut_offsets;
-    std::vector<char> names;
-
-    explicit EveryNodeATip(const pm_panmat* p) : q(*p) {
-        const int32_t N = p->num_nodes;
-        tip_of.resize(N);
-        int32_t extra = 0;
-        for (int32_t v = 0; v < N; ++v) tip_of[v] = p->child_offsets[v] == p->child_offsets[v + 1] ? v : N + extra++;
-        const char* end = p->names;
-        for (int32_t v = 0; v < N; ++v) end += std::strlen(end) + 1;
-        names.assign(p->names, end);
-        names.insert(names.end(), (size_t)extra, '\0');   // (the extra tips' names are never printed)
-        child_offsets.assign(1, 0);
-        for (int32_t v = 0; v < N; ++v) {
-            child_index.insert(child_index.end(), p->child_index + p->child_offsets[v], p->child_index + p->child_offsets[v + 1]);
-            if (tip_of[v] != v) child_index.push_back(tip_of[v]);
-            child_offsets.push_back((int32_t)child_index.size());
-        }
-        child_offsets.insert(child_offsets.end(), (size_t)extra, child_offsets.back());
-        block_mut_offsets.assign(p->block_mut_offsets, p->block_mut_offsets + N + 1);
-        block_mut_offsets.insert(block_mut_offsets.end(), (size_t)extra, block_mut_offsets.back());
-        nuc_mut_offsets.assign(p->nuc_mut_offsets, p->nuc_mut_offsets + N + 1);
-        nuc_mut_offsets.insert(nuc_mut_offsets.end(), (size_t)extra, nuc_mut_offsets.back());
-        q.num_nodes = N + extra;
-        q.child_offsets = child_offsets.data();
-        q.child_index = child_index.data();
-        q.names = names.data();
-        q.block_mut_offsets = block_mut_offsets.data();
-        q.nuc_mut_offsets = nuc_mut_offsets.data();
-        // per-node options play no part (rotate = false) and branch lengths are not read
-        q.circular_offset = nullptr;
-        q.rotation_index = nullptr;
-        q.sequence_inverted = nullptr;
-        q.branch_length = nullptr;
-    }
-};
 
 // The device arrays of one batch's codon tables.
 struct Tables {
@@ -117,32 +76,19 @@ int aa_steps(pm_ctx* c, const pm_panmat* p, int64_t start, int64_t end, const Si
     if (r.columns > (int64_t)0x7fffffff - 64) return fail(c, PM_ERR_UNSUPPORTED, "amino-acid rows of 2^31 columns and more");
 
     // ---- host tables: the row of every node, per (row, block) held / strand, the columns' positions
-    std::vector<int32_t> row_of_tip((size_t)every.q.num_nodes, -1), row_of((size_t)N);
-    for (size_t li = 0; li < r.leaves.size(); ++li) row_of_tip[(size_t)r.leaves[li]] = (int32_t)li;
-    for (int32_t v = 0; v < N; ++v) row_of[(size_t)v] = row_of_tip[(size_t)every.tip_of[(size_t)v]];
+    const std::vector<int32_t> row_of = every.rows_of_nodes(r, N);
     const int32_t rows = (int32_t)r.leaves.size();
     const std::vector<uint8_t> held = held_table(r);
-    std::vector<int32_t> col_main((size_t)r.columns), col_first((size_t)r.columns), rev_top((size_t)M, -1);
+    std::vector<int32_t> col_main, col_first, rev_top((size_t)M, -1);
+    column_positions(r, col_main, col_first);
     // a reverse-strand block that does not start the window is walked from block id 0's last
     // position, as the reference reads sequence[0] (aaTrans.cpp:39-40)
     const int64_t top0 = r.is_block[0] ? (int64_t)r.main_col[0].size() - 1 : -1;
-    host_parallel_for(M, [&](int id) {
-        if (!r.is_block[id]) return;
-        const std::vector<int64_t>& mc = r.main_col[id];
-        for (size_t j = 0; j < mc.size(); ++j)
-            for (int64_t col = r.gap_col[id][j]; col <= mc[j]; ++col) {
-                col_main[(size_t)col] = (int32_t)mc[j];
-                col_first[(size_t)col] = (int32_t)r.gap_col[id][j];
-            }
-        if (top0 >= 0 && top0 < (int64_t)mc.size()) rev_top[(size_t)id] = (int32_t)mc[(size_t)top0];
-    });
-    // the nodes' names back to back: node v's is names[name_at[v] .. name_at[v + 1])
+    for (int32_t id = 0; id < M; ++id)
+        if (r.is_block[id] && top0 >= 0 && top0 < (int64_t)r.main_col[id].size()) rev_top[(size_t)id] = (int32_t)r.main_col[id][(size_t)top0];
     std::vector<char> names;
-    std::vector<int64_t> name_at((size_t)N + 1, 0);
-    for (int32_t v = 0; v < N; ++v) {
-        names.insert(names.end(), r.names[(size_t)v].begin(), r.names[(size_t)v].end());
-        name_at[(size_t)v + 1] = (int64_t)names.size();
-    }
+    std::vector<int64_t> name_at;
+    node_names(r, N, name_at, names);
     std::vector<int32_t> cls[3];   // width classes of k_maf_size
     for (int32_t id = 0; id < M; ++id) {
         if (!r.is_block[id]) continue;

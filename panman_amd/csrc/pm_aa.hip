@@ -37,24 +37,6 @@ __device__ __forceinline__ char aa_letter(const uint8_t* base, int32_t c) {
 
 __device__ __forceinline__ int name_len(char letter) { return letter == '*' ? 1 : 3; }
 
-// exclusive prefix of v over the workgroup's 256 threads, the sum in `total`; sh: kWavesPerBlock words
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* sh, uint32_t& total) {
-    uint32_t wave_total;
-    const uint32_t ex = wave_exclusive_scan(v, wave_total);
-    const int wave = threadIdx.x >> 6;
-    __syncthreads();   // (the last round's readers are done)
-    if ((threadIdx.x & 63) == 0) sh[wave] = wave_total;
-    __syncthreads();
-    uint32_t before = 0;
-    total = 0;
-#pragma unroll
-    for (int k = 0; k < kWavesPerBlock; ++k) {
-        if (k < wave) before += sh[k];
-        total += sh[k];
-    }
-    return ex + before;
-}
-
 __global__ __launch_bounds__(256) void k_aa_locate(AaArgs a) {
     const int lane = threadIdx.x & 63;
     const int64_t v = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
@@ -279,13 +261,6 @@ __device__ __forceinline__ bool deleted(const AaRoot& root, const int32_t* cstar
 
 __device__ __forceinline__ uint32_t entry_len(char kind, int32_t index, char letter) {
     return kind ? 4u + (uint32_t)digits_of((uint32_t)index) + (uint32_t)name_len(letter) : 0u;   // "S:" idx ":" name ";"
-}
-
-__device__ __forceinline__ void put_digits(char* p, uint32_t v, int d) {
-    for (int k = d - 1; k >= 0; --k) {
-        p[k] = (char)('0' + v % 10u);
-        v /= 10u;
-    }
 }
 
 __device__ __forceinline__ void put_entry(char* p, char kind, int32_t index, char letter) {

@@ -134,6 +134,32 @@ __device__ __forceinline__ uint32_t wave_exclusive_scan(uint32_t v, uint32_t& to
     return incl - v;
 }
 
+// exclusive prefix of v over the workgroup's 256 threads, the sum in `total`; sh: 4 words of LDS
+__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* sh, uint32_t& total) {
+    uint32_t wave_total;
+    const uint32_t ex = wave_exclusive_scan(v, wave_total);
+    const int wave = threadIdx.x >> 6;
+    __syncthreads();   // (the last round's readers are done)
+    if ((threadIdx.x & 63) == 0) sh[wave] = wave_total;
+    __syncthreads();
+    uint32_t before = 0;
+    total = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (k < wave) before += sh[k];
+        total += sh[k];
+    }
+    return ex + before;
+}
+
+// v in d decimal digits at p (the text kernels of pm_aa / pm_mutations)
+__device__ __forceinline__ void put_digits(char* p, uint32_t v, int d) {
+    for (int k = d - 1; k >= 0; --k) {
+        p[k] = (char)('0' + v % 10u);
+        v /= 10u;
+    }
+}
+
 // A workgroup barrier that orders LDS only: each wave's LDS accesses are complete (lgkmcnt)
 // and visible to the others, while its global stores and loads stay in flight.  __syncthreads()
 // is a workgroup release / acquire over global memory too, which on gfx950 waits for every

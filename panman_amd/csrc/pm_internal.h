@@ -235,6 +235,7 @@ struct pm_ctx {
     int64_t gfa_batch_bytes = (int64_t)1 << 30;   // pm_gfa: text per device batch of whole P lines (PM_OPT_GFA_BATCH_BYTES)
     int64_t gfa_in_batch_sites = pm::kMaxUploadSites; // pm_gfa_build: block columns per upload and run (PM_OPT_GFA_IN_BATCH_SITES)
     int64_t aa_batch_bytes = (int64_t)1 << 30;    // pm_aa: codon tables and text per device batch of nodes (PM_OPT_AA_BATCH_BYTES)
+    int64_t mutations_batch_bytes = (int64_t)1 << 30;   // pm_print_mutations: entry records and text per device batch of nodes (PM_OPT_MUTATIONS_BATCH_BYTES)
     int64_t subnet_batch_entries = pm::kSubnetBatchEntries;   // pm_subnet: expanded bases sorted per batch (PM_OPT_SUBNET_BATCH_ENTRIES)
 };
 
@@ -679,6 +680,63 @@ struct AaText {
 hipError_t launch_aa_line_len(pm_ctx* c, const AaArgs& a, const AaTables& root, const AaTables& t, const AaText& x);
 hipError_t launch_aa_write(pm_ctx* c, const AaArgs& a, const AaTables& root, const AaTables& t, const AaText& x);
 hipError_t warm_aa();
+// Mutation printing (pm_mutations.hip; Tree::printMutationsNew, src/panman.cpp:3699-4057) over the
+// replayed rows of every node.  A cell (block, position, slot) of the reference's maps is a column
+// of the canonical row: main_col[pos_off[block] + position], or gap_col[..] + slot.
+constexpr int32_t kMutChunk = 256;       // columns per workgroup of the root map's two passes
+constexpr int32_t kMutRound = 256;       // entries per round of k_mut_write's workgroup
+constexpr uint8_t kMutGap = 1, kMutOdd = 2;   // MutEntry::flags
+struct MutEntry {                  // one element of a nucleotide mutation
+    int32_t coord1;                // the root coordinate it prints (coord + 1)
+    uint8_t kind;                  // 0: no entry; 1, 2, 3: line S, I, D
+    char old_ch, new_ch;
+    uint8_t flags;                 // kMutGap: "g"; kMutOdd: a kept NSNPS over no base
+};
+static_assert(sizeof(MutEntry) == 8, "MutEntry is 8 bytes");
+struct MutArgs {
+    const char* rows;
+    int64_t row_stride, columns;
+    int32_t nodes, blocks, root;   // blocks: ids 0..max_id
+    const int32_t* row_of;         // [nodes]
+    const int32_t* parent;         // [nodes]
+    const uint8_t* held;           // [nodes][blocks] kMafHeld | kMafForward, as getSequenceFromReference leaves them
+    const int64_t* blk_lo;         // [blocks]
+    const int64_t* blk_hi;
+    const int64_t* pos_off;        // [blocks + 1] into main_col / gap_col (a block's positions 0..n_b)
+    const int32_t* main_col;
+    const int32_t* gap_col;
+    // the root map: real characters of the root's held blocks
+    const uint8_t* col_held;       // [columns] 1: the root holds the column's block
+    int64_t* chunk;                // [chunks of kMutChunk columns] their real characters; then the exclusive scan
+    int32_t* before;               // [columns + 1] the real characters before the column
+    // the tree's nucleotide mutations in list order
+    const int32_t* mut_node;
+    const int32_t* mut_primary;
+    const int32_t* mut_position;
+    const int32_t* mut_gap;
+    const uint8_t* mut_info;
+    const uint32_t* mut_nucs;
+    unsigned long long* odd;       // [1] kept NSNPS entries whose old character is no base
+    int32_t* error;                // [1] set when a mutation's cell does not exist
+};
+hipError_t launch_mut_root_map(pm_ctx* c, const MutArgs& a);
+// One batch: the mutations [m0, m0 + m) of nodes [v0, v0 + n).
+struct MutBatch {
+    int64_t m0, m, entries;
+    int32_t v0, n;
+    const int64_t* node_mut;       // [nodes + 1] the PanMAT's nuc_mut_offsets
+    int64_t* elems;                // [m + 1] elements per mutation (the last 0); then the exclusive scan
+    MutEntry* entry;               // [entries]
+    const int64_t* name_off;       // [nodes + 1] into names
+    const char* names;
+    int64_t* line_len;             // [3 n + 1] bytes of node s's line k at 3 s + k (the last 0); then the scan
+    char* text;
+};
+hipError_t launch_mut_count(pm_ctx* c, const MutArgs& a, const MutBatch& b);
+hipError_t launch_mut_classify(pm_ctx* c, const MutArgs& a, const MutBatch& b);
+hipError_t launch_mut_line_len(pm_ctx* c, const MutArgs& a, const MutBatch& b);
+hipError_t launch_mut_write(pm_ctx* c, const MutArgs& a, const MutBatch& b);
+hipError_t warm_mutations();
 // rows[leaf][c0 .. c0+n) chars -> packed codes out[leaf][(n+1)/2] ('-', 'x' -> 0)
 hipError_t launch_rows_to_codes(pm_ctx* c, const char* rows, int64_t row_stride, int32_t leaves, int64_t c0,
                                 int64_t n, uint8_t* out, int64_t out_stride);
