@@ -12,7 +12,7 @@
 // or 16 B (leaf / final codes) through fully coalesced 1 KiB wave-instructions.  Levels
 // (heights for the post-order, depths for the pre-order) are separate launches.
 // Integer bit-set work only: no MFMA (SURVEY.md §8d roofline is HBM bandwidth).
-#include "pm_kernels.h"
+#include "pm_launch.h"
 
 #if PM_NT_LOADS   // (pm_fitch_nt.hip: the same passes, non-temporal set-record loads)
 #define launch_fitch launch_fitch_nt
@@ -701,356 +701,67 @@ __global__ __launch_bounds__(kScoreBlock) void k_site_score(const pm_mut* recs, 
 
 }  // namespace
 
-hipError_t launch_fitch(pm_ctx* c, bool block) {
-    const HostTree& ht = c->ht;
-    const DevTree& dt = c->dt;
-    const int32_t tiles = (c->words + kWave - 1) / kWave;
-    const int64_t wpad = (int64_t)tiles * kWave;
-
-    // Fitch (not block Fitch) may skip materialising leaf-parents and, with every leaf
-    // present, S2 / S3 subtrees (the subtree form)
-    const bool virt = !block && c->virtual_leaf_parents;
-    const bool sub = virt && c->subtree_form && c->leaves_all_present && ht.num_sshape > 0;
-    const int32_t* child_enc = sub ? dt.child_enc_k : virt ? dt.child_enc_v : dt.child_enc;
-    // subtree form: LDS-staged sweeps above the plan's first level (PM_OPT_CLUSTER), the levels
-    // below them one launch per height; else grouped post-order launches (PM_OPT_UP_GROUP) or one
-    // launch per height
-    // (with a sweep plan the grouped order stops below the sweeps: without them, one launch per
-    // height)
-    const ClusterPlan& cl = ht.cl;
-    const bool planned = cl.band_wg.size() > 1;
-    const bool clu = sub && c->cluster && planned;
-    const bool grp = sub && c->up_group && (clu || !planned);
-    const NodeDesc* up_desc = grp ? dt.up_desc_g : sub ? dt.up_desc_k : virt ? dt.up_desc_v : dt.up_desc;
-    // PM_OPT_SUB_DOWN: S2 / S3 children stay in their parent's pre-order descriptor (k_down<..,
-    // SUB>) and leave the tail
-    const bool sub_down = sub && c->sub_down;
-    const NodeDesc* down_desc = sub_down ? dt.down_desc_ks : sub ? dt.down_desc_k : virt ? dt.down_desc_v : dt.down_desc;
-    const std::vector<int32_t>& up_off = grp ? ht.up_level_off_g : sub ? ht.up_level_off_k : virt ? ht.up_level_off_v : ht.up_level_off;
-    const std::vector<int32_t>& down_off = sub ? ht.down_level_off_k : virt ? ht.down_level_off_v : ht.down_level_off;
-
-    const bool ap = c->leaves_all_present;
-    UpArgs up{};
-    up.child_off = dt.child_off;
-    up.child_enc = child_enc;
-    up.leaf_flag = c->leaf_flag;
-    up.leaf_planes = c->leaf_planes;
-    up.leaf_present = c->leaf_present;
-    up.sets = reinterpret_cast<uint4*>(c->sets);
-    up.cmask = c->cmask;
-    up.vleaf = reinterpret_cast<const int4*>(dt.vleaf);
-    up.cons = c->cons;
-    up.forced = (c->has_forced && !block) ? c->forced : nullptr;   // refState (M1); blocks force in backward
-    up.absent_code0 = false;
-    up.all_present = c->leaves_all_present;
-    up.root_dense = dt.root_dense;
-    up.tiles = tiles;
-    up.wpad = wpad;
-    const std::vector<int32_t>& class_off = grp ? ht.up_class_off_g : sub ? ht.up_class_off_k : virt ? ht.up_class_off_v : ht.up_class_off;
-    const int form = sub ? 2 : virt ? 1 : 0;   // pre-order level tables (lvl_down)
-    const int up_form = grp ? 3 : form;        // post-order ones (lvl_up)
-    up.desc_all = up_desc;
-    // up slots: the subtree form's kernels (alloc_work sizes them for its two up orders)
-    if (sub && c->upm == nullptr) return hipErrorInvalidValue;
-    up.upm = sub ? c->upm : nullptr;
-    up.pslot = grp ? (clu ? dt.pslot_gc : dt.pslot_g) : clu ? dt.pslot_kc : dt.pslot_k;
-    const int H = clu && !grp ? cl.h0 : (int)up_off.size() - 1;   // (the grouped order holds the levels below h0 only)
-    // runs of >= 2 narrow levels (PM_OPT_NARROW): one band launch each
-    auto narrow_up = [&](int h) {
-        const int32_t b = class_off[h * kDegreeClasses], m = class_off[h * kDegreeClasses + 1],
-                      e = class_off[(h + 1) * kDegreeClasses];
-        return (m - b) + 4 * (e - m) <= c->narrow_max;
-    };
-    for (int h = 0; h < H; ++h) {
-        if (c->narrow_max > 0 && narrow_up(h)) {
-            int h1 = h + 1;
-            while (h1 < H && narrow_up(h1)) ++h1;
-            if (h1 - h >= 2) {
-                up.desc = up_desc;
-                const int32_t* tab = dt.lvl + ht.lvl_up[up_form];
-                timer_begin(c, 0);
-                if (grp) hipLaunchKernelGGL((k_fitch_up_band<true, true, true>), dim3(tiles), dim3(kBandBlock), 0, c->stream, up, tab, h, h1);
-                else if (sub) hipLaunchKernelGGL((k_fitch_up_band<true, true>), dim3(tiles), dim3(kBandBlock), 0, c->stream, up, tab, h, h1);
-                else if (ap) hipLaunchKernelGGL((k_fitch_up_band<true, false>), dim3(tiles), dim3(kBandBlock), 0, c->stream, up, tab, h, h1);
-                else hipLaunchKernelGGL((k_fitch_up_band<false, false>), dim3(tiles), dim3(kBandBlock), 0, c->stream, up, tab, h, h1);
-                timer_end(c, 0);
-                h = h1 - 1;
-                continue;
-            }
+// Executes the schedule's steps (pm_schedule.cpp decides them; the pre-order half: pm_launch.h).
+hipError_t launch_fitch(pm_ctx* c, const Schedule& s) {
+    const RunPaths& p = s.paths;
+    const bool grp = p.grp, sub = p.sub, ap = p.ap;
+    const DevForm f = dev_form(c, p);
+    const dim3 kb(kBlock);
+    UpArgs up = fill_up_args(c, p, f);
+    up.forced = (c->has_forced && !p.block) ? c->forced : nullptr;   // refState (M1); blocks force in backward
+    hipError_t e = run_steps(c, s, 0, s.first_down, [&](const Step& st, hipStream_t q) {
+        const dim3 grid = step_grid(st, up.tiles);
+        UpArgs a = up;
+        a.desc = f.up_desc + st.first;
+        a.count = st.count;
+        switch (st.kind) {
+        case StepKind::kUpBand: {   // a run of narrow levels: one workgroup per tile
+            a.desc = f.up_desc;
+            const dim3 tg(st.grid_x), tb(kBandBlock);
+            if (grp) hipLaunchKernelGGL((k_fitch_up_band<true, true, true>), tg, tb, 0, q, a, f.lvl_up, st.h0, st.h1);
+            else if (sub) hipLaunchKernelGGL((k_fitch_up_band<true, true>), tg, tb, 0, q, a, f.lvl_up, st.h0, st.h1);
+            else if (ap) hipLaunchKernelGGL((k_fitch_up_band<true, false>), tg, tb, 0, q, a, f.lvl_up, st.h0, st.h1);
+            else hipLaunchKernelGGL((k_fitch_up_band<false, false>), tg, tb, 0, q, a, f.lvl_up, st.h0, st.h1);
+            break;
         }
-        // out-degree <= 3: one wave per (node, tile); wider: one workgroup per (node, tile)
-        const int32_t b = class_off[h * kDegreeClasses], m = class_off[h * kDegreeClasses + 1],
-                      e = class_off[(h + 1) * kDegreeClasses];
-        if (m > b && e > m && (int64_t)(m - b) * tiles <= kMixedMaxWaves) {   // both kinds: one launch
-            up.desc = up_desc + b;
-            up.count = m - b;
-            const int32_t nb = (int32_t)wave_grid(up.count, tiles).x;
-            const dim3 grid((unsigned)(nb + (int64_t)(e - m) * tiles));
-            timer_begin(c, 0);
-            if (grp) hipLaunchKernelGGL((k_fitch_up_mixed<true, true, true>), grid, dim3(kBlock), 0, c->stream, up, up_desc + m, nb);
-            else if (sub) hipLaunchKernelGGL((k_fitch_up_mixed<true, true>), grid, dim3(kBlock), 0, c->stream, up, up_desc + m, nb);
-            else if (ap) hipLaunchKernelGGL((k_fitch_up_mixed<true, false>), grid, dim3(kBlock), 0, c->stream, up, up_desc + m, nb);
-            else hipLaunchKernelGGL((k_fitch_up_mixed<false, false>), grid, dim3(kBlock), 0, c->stream, up, up_desc + m, nb);
-            timer_end(c, 0);
-            continue;
+        case StepKind::kUpMixed: {   // a level's narrow and wide nodes in one launch
+            const dim3 mg(st.grid_x);
+            const NodeDesc* wdesc = a.desc + st.count;
+            const int32_t nb = (int32_t)wave_grid_x(st.count, up.tiles);
+            if (grp) hipLaunchKernelGGL((k_fitch_up_mixed<true, true, true>), mg, kb, 0, q, a, wdesc, nb);
+            else if (sub) hipLaunchKernelGGL((k_fitch_up_mixed<true, true>), mg, kb, 0, q, a, wdesc, nb);
+            else if (ap) hipLaunchKernelGGL((k_fitch_up_mixed<true, false>), mg, kb, 0, q, a, wdesc, nb);
+            else hipLaunchKernelGGL((k_fitch_up_mixed<false, false>), mg, kb, 0, q, a, wdesc, nb);
+            break;
         }
-        // a level's narrow and wide nodes are independent: the wide launch runs beside the
-        // narrow one on the side stream (parallel graph branches) instead of after it
-#ifdef PM_NO_SIDE
-        const bool fork = false;
-#else
-        const bool fork = m > b && e > m;
-#endif
-        if (fork) {
-            const hipError_t fe = side_fork(c);
-            if (fe != hipSuccess) return fe;
+        case StepKind::kUpWide:   // out-degree > 3: one workgroup per (node, tile)
+            if (ap) hipLaunchKernelGGL(k_fitch_up_wide<true>, grid, kb, 0, q, a);
+            else hipLaunchKernelGGL(k_fitch_up_wide<false>, grid, kb, 0, q, a);
+            break;
+        case StepKind::kUpNarrow:   // out-degree <= 3: one wave per (node, tile)
+            if (st.variant == kNarrowPlain) hipLaunchKernelGGL((k_fitch_up<true, false, true, false, true>), grid, kb, 0, q, a);
+            else if (sub && st.variant == kNarrowLeafy) hipLaunchKernelGGL((k_fitch_up<true, true, true>), grid, kb, 0, q, a);
+            else if (st.variant == kNarrowRecomp) hipLaunchKernelGGL((k_fitch_up<true, false, true, true>), grid, kb, 0, q, a);
+            else if (sub) hipLaunchKernelGGL((k_fitch_up<true, false, true>), grid, kb, 0, q, a);
+            else if (st.variant == kNarrowLeafy) hipLaunchKernelGGL((k_fitch_up<true, true>), grid, kb, 0, q, a);
+            else if (ap) hipLaunchKernelGGL((k_fitch_up<true, false>), grid, kb, 0, q, a);
+            else hipLaunchKernelGGL((k_fitch_up<false, false>), grid, kb, 0, q, a);
+            break;
+        case StepKind::kUpSweep: {   // one band of the LDS-staged sweeps
+            const ClArgs ca{c->dt.cl_items, c->dt.cl_wg_off, c->dt.cl_slot_of, c->dt.cl_pslot, c->ht.cl.upm_base, st.first};
+            hipLaunchKernelGGL(k_fitch_up_cluster, dim3(st.grid_x), dim3(kWave), 0, q, up, ca);
+            break;
         }
-        if (e > m) {
-            UpArgs w = up;
-            w.desc = up_desc + m;
-            w.count = e - m;
-            const dim3 grid = block_grid(w.count, tiles);
-            hipStream_t s = fork ? c->side : c->stream;
-            if (!fork) timer_begin(c, 0);
-            if (ap) hipLaunchKernelGGL(k_fitch_up_wide<true>, grid, dim3(kBlock), 0, s, w);
-            else hipLaunchKernelGGL(k_fitch_up_wide<false>, grid, dim3(kBlock), 0, s, w);
-            if (!fork) timer_end(c, 0);
+        default:
+            break;
         }
-        if (m > b) {
-            const bool leafy = grp ? ht.up_leafy_g[h] : sub ? ht.up_leafy_k[h] : virt && ht.up_leafy_v[h];
-            // the grouped order's plain prefix (binary, no S2 / S3 child, nothing recomputed):
-            // the lean kernel, then the rest of the class
-            int32_t np = grp && !leafy && c->plain_up ? std::min(ht.up_plain_g[h], m - b) : 0;
-            if ((int64_t)np * tiles < (c->plain_min_waves > 0 ? c->plain_min_waves : kPlainMinWaves)) np = 0;
-            timer_begin(c, 0);
-            if (np > 0) {
-                up.desc = up_desc + b;
-                up.count = np;
-                hipLaunchKernelGGL((k_fitch_up<true, false, true, false, true>), wave_grid(np, tiles), dim3(kBlock), 0, c->stream, up);
-            }
-            up.desc = up_desc + b + np;
-            up.count = m - b - np;
-            const dim3 grid = wave_grid(up.count, tiles);
-            if (up.count == 0) {
-                if (fork) {
-                    const hipError_t je = side_join(c);
-                    if (je != hipSuccess) return je;
-                }
-                timer_end(c, 0);
-                continue;
-            }
-            if (sub && leafy) hipLaunchKernelGGL((k_fitch_up<true, true, true>), grid, dim3(kBlock), 0, c->stream, up);
-            else if (grp && ht.up_recomp_g[h]) hipLaunchKernelGGL((k_fitch_up<true, false, true, true>), grid, dim3(kBlock), 0, c->stream, up);
-            else if (sub) hipLaunchKernelGGL((k_fitch_up<true, false, true>), grid, dim3(kBlock), 0, c->stream, up);
-            else if (ap && leafy) hipLaunchKernelGGL((k_fitch_up<true, true>), grid, dim3(kBlock), 0, c->stream, up);
-            else if (ap) hipLaunchKernelGGL((k_fitch_up<true, false>), grid, dim3(kBlock), 0, c->stream, up);
-            else hipLaunchKernelGGL((k_fitch_up<false, false>), grid, dim3(kBlock), 0, c->stream, up);
-            if (fork) {
-                const hipError_t je = side_join(c);
-                if (je != hipSuccess) return je;
-            }
-            timer_end(c, 0);
-        }
-    }
-
-    if (clu) {   // the sweeps, band by band
-        const ClArgs ca0{dt.cl_items, dt.cl_wg_off, dt.cl_slot_of, dt.cl_pslot, cl.upm_base, 0};
-        for (size_t bnd = 0; bnd + 1 < cl.band_wg.size(); ++bnd) {
-            ClArgs ca = ca0;
-            ca.wg0 = cl.band_wg[bnd];
-            const int64_t nwg = cl.band_wg[bnd + 1] - ca.wg0;
-            if (nwg == 0) continue;
-            timer_begin(c, 0);
-            hipLaunchKernelGGL(k_fitch_up_cluster, dim3((unsigned)(nwg * tiles)), dim3(kWave), 0, c->stream, up, ca);
-            timer_end(c, 0);
-        }
-    }
-
-    hipError_t e = hipMemsetAsync(c->shard_cnt, 0, sizeof(uint32_t) * kShards, c->stream);
+    });
+    if (e == hipSuccess) e = run_down<true>(c, s, f, (c->has_forced && p.block) ? c->forced : nullptr, false);
     if (e != hipSuccess) return e;
-    DownArgs dn{};
-    dn.child_off = dt.child_off;
-    dn.child_enc = child_enc;
-    dn.parent_dense = dt.parent_dense;
-    dn.internal_id = dt.internal_id;
-    dn.leaf_id = dt.leaf_id;
-    dn.leaf_flag = c->leaf_flag;
-    dn.leaf_planes = c->leaf_planes;
-    dn.leaf_present = c->leaf_present;
-    dn.sets = reinterpret_cast<uint4*>(c->sets);
-    dn.cmask = c->cmask;
-    dn.root_final = c->root_final;
-    dn.dense_base = -1;
-    dn.cons = c->cons;
-    dn.root_dense = dt.root_dense;
-    dn.tiles = tiles;
-    dn.wpad = wpad;
-    dn.words = c->words;
-    dn.sites = c->num_sites;
-    dn.recs = c->recs;
-    dn.shard_cap = c->shard_cap;
-    dn.shard_cnt = c->shard_cnt;
-    dn.root_code = c->root_code;
-    dn.forced = (c->has_forced && block) ? c->forced : nullptr;
-    dn.absent_code0 = false;
-    dn.all_present = c->leaves_all_present;
-    dn.vleaf = reinterpret_cast<const int4*>(dt.vleaf);
-    dn.vinner = dt.vinner;
-    if (sub_down) {   // the S children's leaf words and node ids (their tail descriptors)
-        dn.tail = dt.tail_desc_k;
-        dn.num_s = ht.num_tail_s;
-        dn.sbase = ht.sbase;
-        dn.sub_planes = c->sub_planes;
-    }
-    // pre-order sweeps over the post-order's clusters (every level swept), the bands top-down
-    const bool cld = clu && cl.down && !sub_down;
-    if (cld) {
-        for (size_t bnd = cl.band_wg.size() - 1; bnd-- > 0;) {
-            const ClDownArgs ca{dt.cl_down_items, dt.cl_wg_off, cl.band_wg[bnd]};
-            const int64_t nwg = cl.band_wg[bnd + 1] - ca.wg0;
-            if (nwg == 0) continue;
-            timer_begin(c, 1);
-            hipLaunchKernelGGL(k_down_cluster<Mode::kFitch>, dim3((unsigned)(nwg * tiles)), dim3(kWave), 0, c->stream, dn, ca);
-            timer_end(c, 1);
-        }
-    }
-    const int D = cld ? 0 : (int)down_off.size() - 1;
-    // packed levels (PM_OPT_DOWN_PACK): ungrouped, non-band launches of k_down<Fitch, AP, DENSE>
-    const bool pack_form = !kCxCompact && !block && ap && !sub_down;
-    const int64_t down_pack_min = c->down_pack_min_waves != 0 ? c->down_pack_min_waves : kDownPackMinWaves;
-    int packed_levels = 0;
-    c->down_pack_ranges.clear();
-    for (int d = 0; d < D; ++d) {
-        if (c->narrow_max > 0 && down_off[d + 1] - down_off[d] <= c->narrow_max) {
-            int d1 = d + 1;
-            while (d1 < D && down_off[d1 + 1] - down_off[d1] <= c->narrow_max) ++d1;
-            if (d1 - d >= 2) {
-                dn.desc = down_desc;
-                const int32_t* tab = dt.lvl + ht.lvl_down[form];
-                const int32_t* base = sub ? (ht.down_dense_k ? dt.lvl + ht.lvl_base_k : nullptr)
-                                          : (virt && ht.down_dense_v) ? tab : nullptr;
-                timer_begin(c, 1);
-                // (subtree form: the lean body as in the level kernels, S2 / S3 records in k_tail)
-                if (block && ap) hipLaunchKernelGGL((k_down_band<Mode::kBlockFitch, true>), dim3(tiles), dim3(kBandBlock), 0, c->stream, dn, tab, base, d, d1);
-                else if (block) hipLaunchKernelGGL((k_down_band<Mode::kBlockFitch, false>), dim3(tiles), dim3(kBandBlock), 0, c->stream, dn, tab, base, d, d1);
-                // (level groups inside the band when PM_OPT_GROUP_WAVES is on)
-                else if (sub_down && c->group_waves > 0) hipLaunchKernelGGL((k_down_band<Mode::kFitch, true, true, true>), dim3(tiles), dim3(kBandBlock), 0, c->stream, dn, tab, base, d, d1);
-                else if (sub_down) hipLaunchKernelGGL((k_down_band<Mode::kFitch, true, true>), dim3(tiles), dim3(kBandBlock), 0, c->stream, dn, tab, base, d, d1);
-                else if (ap && c->group_waves > 0) hipLaunchKernelGGL((k_down_band<Mode::kFitch, true, false, true>), dim3(tiles), dim3(kBandBlock), 0, c->stream, dn, tab, base, d, d1);
-                else if (ap) hipLaunchKernelGGL((k_down_band<Mode::kFitch, true>), dim3(tiles), dim3(kBandBlock), 0, c->stream, dn, tab, base, d, d1);
-                else if (c->group_waves > 0) hipLaunchKernelGGL((k_down_band<Mode::kFitch, false, false, true>), dim3(tiles), dim3(kBandBlock), 0, c->stream, dn, tab, base, d, d1);
-                else hipLaunchKernelGGL((k_down_band<Mode::kFitch, false>), dim3(tiles), dim3(kBandBlock), 0, c->stream, dn, tab, base, d, d1);
-                timer_end(c, 1);
-                d = d1 - 1;
-                continue;
-            }
-        }
-        dn.desc = down_desc + down_off[d];
-        dn.count = down_off[d + 1] - down_off[d];
-        if (dn.count == 0) continue;
-        // level d = one range of dense indices: [down_off[d], down_off[d+1]) in the leaf-parent
-        // form, from down_dense_base_k[d] in the subtree form
-        const bool dense = sub ? ht.down_dense_k : virt && ht.down_dense_v;
-        dn.dense_base = !dense ? -1 : sub ? ht.down_dense_base_k[d] : down_off[d];
-        // levels d .. d + g - 1 in one launch (PM_OPT_GROUP_*), none of them starting a band
-        auto narrow_down = [&](int l) { return c->narrow_max > 0 && down_off[l + 1] - down_off[l] <= c->narrow_max; };
-        auto band_at = [&](int l) { return narrow_down(l) && l + 1 < D && narrow_down(l + 1); };
-        int g = 1;
-        int64_t items = dn.count;
-        while (!block && c->group_waves > 0 && g < std::min(c->group_levels, kGroupLevels) && d + g < D) {
-            const int32_t ng = down_off[d + g + 1] - down_off[d + g];
-            if (ng == 0 || (items + ng) * tiles > c->group_waves || band_at(d + g)) break;
-            items += ng;
-            ++g;
-        }
-        if (g > 1) {
-            for (int k = 0; k < 4; ++k) {
-                const int l = std::min(d + k, d + g - 1);
-                if (k > 0) dn.split[k - 1] = k < g ? down_off[d + k] - down_off[d] : (int32_t)items;
-                dn.dense_g[k] = !dense ? -1 : sub ? ht.down_dense_base_k[l] : down_off[l];
-            }
-            dn.count = (int32_t)items;
-            const dim3 grid = wave_grid(dn.count, tiles);
-            timer_begin(c, 1);
-            if (sub_down && dense) hipLaunchKernelGGL((k_down<Mode::kFitch, true, true, true, true>), grid, dim3(kBlock), 0, c->stream, dn);
-            else if (sub_down) hipLaunchKernelGGL((k_down<Mode::kFitch, true, false, true, true>), grid, dim3(kBlock), 0, c->stream, dn);
-            else if (ap && dense) hipLaunchKernelGGL((k_down<Mode::kFitch, true, true, false, true>), grid, dim3(kBlock), 0, c->stream, dn);
-            else if (ap) hipLaunchKernelGGL((k_down<Mode::kFitch, true, false, false, true>), grid, dim3(kBlock), 0, c->stream, dn);
-            else hipLaunchKernelGGL((k_down<Mode::kFitch, false, false, false, true>), grid, dim3(kBlock), 0, c->stream, dn);
-            timer_end(c, 1);
-            d += g - 1;
-            continue;
-        }
-        // PM_OPT_DOWN_PACK: a large dense level of the lean all-present kernel, below the root's,
-        // in groups of kDownPack items per wave (k_down<.., G>)
-        const bool packs = pack_form && dense && d > 0 && (int64_t)dn.count * tiles >= down_pack_min;
-        if (packs) {   // (kept for pm_design_bytes: the levels the option takes, or would take)
-            c->down_pack_ranges.push_back(dn.dense_base);
-            c->down_pack_ranges.push_back(dn.count);
-        }
-        if (packs && c->down_pack) {
-            const dim3 grid = wave_grid((dn.count + kDownPack - 1) / kDownPack, tiles);
-            timer_begin(c, 1);
-            hipLaunchKernelGGL((k_down<Mode::kFitch, true, true, false, false, kDownPack>), grid, dim3(kBlock), 0, c->stream, dn);
-            timer_end(c, 1);
-            ++packed_levels;
-            continue;
-        }
-        const dim3 grid = wave_grid(dn.count, tiles);
-        timer_begin(c, 1);
-        // (subtree form: the levels' descriptors omit S2 / S3 children, whose records come
-        // from the tail launch, so the lean kernels run every level)
-        if (block && ap) hipLaunchKernelGGL((k_down<Mode::kBlockFitch, true, false>), grid, dim3(kBlock), 0, c->stream, dn);
-        else if (block) hipLaunchKernelGGL((k_down<Mode::kBlockFitch, false, false>), grid, dim3(kBlock), 0, c->stream, dn);
-        else if (sub_down && dense) hipLaunchKernelGGL((k_down<Mode::kFitch, true, true, true>), grid, dim3(kBlock), 0, c->stream, dn);
-        else if (sub_down) hipLaunchKernelGGL((k_down<Mode::kFitch, true, false, true>), grid, dim3(kBlock), 0, c->stream, dn);
-        else if (ap && dense) hipLaunchKernelGGL((k_down<Mode::kFitch, true, true>), grid, dim3(kBlock), 0, c->stream, dn);
-        else if (ap) hipLaunchKernelGGL((k_down<Mode::kFitch, true, false>), grid, dim3(kBlock), 0, c->stream, dn);
-        else hipLaunchKernelGGL((k_down<Mode::kFitch, false, false>), grid, dim3(kBlock), 0, c->stream, dn);
-        timer_end(c, 1);
-    }
-    phase_add("run.down_pack", packed_levels > 0 ? (double)kDownPack : 0.0);   // the group size the packed levels took (0: none packed)
-    phase_add("run.down_pack_launches", (double)packed_levels);
-    // The tail (children beyond the second, S2 / S3 subtrees) needs only its parents'
-    // finals: one flat launch after the levels.
-    // (PM_OPT_SUB_DOWN: the S2 / S3 items, the first num_tail_s, were done by the levels)
-    // (PM_OPT_TAIL_PACK: the S2 / S3 items in groups per wave, k_tail<.., G>; the other items
-    // -- leaf-ish children beyond the second -- after them, one wave each as before)
-    const int64_t pack_min = c->tail_pack_min_waves != 0 ? c->tail_pack_min_waves : kTailPackMinWaves;
-    const bool pack = sub && !sub_down && c->tail_pack && ht.num_tail_s > 0 && (int64_t)ht.num_tail_s * tiles >= pack_min;
-    constexpr int G = kTailPack;
-    phase_add("run.tail_pack", pack ? (double)G : 0.0);   // the group size a launch sequence took (0: one wave per item)
-    phase_add("run.tail_s_waves", sub ? (double)ht.num_tail_s * tiles : 0.0);   // ... and what the threshold is compared with
-    if (pack) {
-        DownArgs t = dn;
-        t.tail = dt.tail_desc_k;
-        t.num_s = ht.num_tail_s;
-        t.count = (ht.num_tail_s + G - 1) / G;
-        t.sbase = ht.sbase;
-        t.sub_planes = c->sub_planes;
-        const dim3 grid = wave_grid(t.count, tiles);
-        timer_begin(c, 5);
-        hipLaunchKernelGGL((k_tail<Mode::kFitch, true, true, G>), grid, dim3(kBlock), 0, c->stream, t);
-        timer_end(c, 5);
-    }
-    const int32_t tail_skip = sub_down || pack ? ht.num_tail_s : 0;
-    const int32_t tail_total = (sub ? ht.num_tail_k : virt ? ht.num_tail_v : ht.num_tail) - tail_skip;
-    if (tail_total > 0) {
-        DownArgs t = dn;
-        t.tail = (sub ? dt.tail_desc_k : virt ? dt.tail_desc_v : dt.tail_desc) + tail_skip;
-        t.count = tail_total;
-        t.num_s = sub && !sub_down && !pack ? ht.num_tail_s : 0;
-        t.sbase = ht.sbase;
-        t.sub_planes = c->sub_planes;
-        const dim3 grid = wave_grid(t.count, tiles);
-        timer_begin(c, 5);
-        if (sub) hipLaunchKernelGGL((k_tail<Mode::kFitch, true, true>), grid, dim3(kBlock), 0, c->stream, t);
-        else if (block && ap) hipLaunchKernelGGL((k_tail<Mode::kBlockFitch, true>), grid, dim3(kBlock), 0, c->stream, t);
-        else if (block) hipLaunchKernelGGL((k_tail<Mode::kBlockFitch, false>), grid, dim3(kBlock), 0, c->stream, t);
-        else if (ap) hipLaunchKernelGGL((k_tail<Mode::kFitch, true>), grid, dim3(kBlock), 0, c->stream, t);
-        else hipLaunchKernelGGL((k_tail<Mode::kFitch, false>), grid, dim3(kBlock), 0, c->stream, t);
-        timer_end(c, 5);
-    }
+    phase_add("run.down_pack", s.packed_levels > 0 ? (double)kDownPack : 0.0);   // the group size the packed levels took (0: none packed)
+    phase_add("run.down_pack_launches", (double)s.packed_levels);
+    phase_add("run.tail_pack", s.tail_pack ? (double)kTailPack : 0.0);   // the group size a launch sequence took (0: one wave per item)
+    phase_add("run.tail_s_waves", (double)s.tail_s_waves);   // ... and what the threshold is compared with
     return hipGetLastError();
 }
 

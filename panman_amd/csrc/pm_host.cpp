@@ -242,46 +242,35 @@ int alloc_work(pm_ctx* c, int mode) {
     return PM_OK;
 }
 
-// Non-temporal set-record loads (pm_fitch_nt.hip / pm_sankoff_nt.hip) when the tree has a
-// level of at least 64k (node, tile) waves: there the records a wave reads have left the
-// caches anyway (N* Fitch 14.7 -> 14.06 ms); a tree of small levels (C3: <= ~900 nodes x 15
-// tiles) reads them back from cache and keeps ordinary loads (C3 Fitch 4.42 -> 4.30 ms).
-bool nt_policy(const pm_ctx* c) {
-    if (c->nt_loads >= 0) return c->nt_loads != 0;
-    const std::vector<int32_t>& off = c->ht.down_level_off;
-    int64_t widest = 0;
-    for (size_t l = 0; l + 1 < off.size(); ++l) widest = std::max<int64_t>(widest, off[l + 1] - off[l]);
-    return widest * (wpad_of(c) / kWave) >= 65536;
-}
-
+// The run's schedule (pm_schedule.cpp), executed by the build of the passes it names: ordinary
+// or non-temporal set-record loads (pm_fitch_nt.hip / pm_sankoff_nt.hip; RunPaths::nt).
 hipError_t launch_all(pm_ctx* c, int mode) {
-    const bool sankoff = mode == PM_MODE_SANKOFF || mode == PM_MODE_BLOCK_SANKOFF;
-    const bool block = mode == PM_MODE_BLOCK_FITCH || mode == PM_MODE_BLOCK_SANKOFF;
-    const bool nt = nt_policy(c);
+    const Schedule s = schedule_run(c->ht, run_opts_of(c), mode);
+    // up slots: the subtree form's kernels (alloc_work sizes them for its up orders)
+    if (s.paths.sub && c->upm == nullptr) return hipErrorInvalidValue;
+    const bool nt = s.paths.nt;
     phase_add("run.nt_loads", nt ? 1.0 : 0.0);   // which build of the passes a launch sequence took
-    hipError_t e = sankoff ? (nt ? launch_sankoff_nt(c, block) : launch_sankoff(c, block))
-                           : (nt ? launch_fitch_nt(c, block) : launch_fitch(c, block));
+    hipError_t e = s.paths.sankoff ? (nt ? launch_sankoff_nt(c, s) : launch_sankoff(c, s))
+                                   : (nt ? launch_fitch_nt(c, s) : launch_fitch(c, s));
     if (e == hipSuccess) e = launch_score(c);
     return e;
 }
 
 // Everything a captured run depends on: a different value means a different graph.
 uint64_t graph_key_of(const pm_ctx* c, int mode) {
-    const uint64_t parts[] = {(uint64_t)mode, (uint64_t)c->virtual_leaf_parents, (uint64_t)c->subtree_form,
-                              (uint64_t)c->narrow_max, (uint64_t)c->group_waves, (uint64_t)c->group_levels, (uint64_t)c->up_group,
-                              (uint64_t)c->sub_down, (uint64_t)c->tail_pack, (uint64_t)c->tail_pack_min_waves, (uint64_t)c->down_pack, (uint64_t)c->down_pack_min_waves, (uint64_t)c->plain_up, (uint64_t)c->plain_min_waves, (uint64_t)c->cluster,
-                              (uint64_t)(uintptr_t)c->upm,
-                              (uint64_t)(uintptr_t)c->sk_parts,
-                              (uint64_t)c->leaves_all_present, (uint64_t)c->has_forced, (uint64_t)c->num_sites,
+    const RunOpts o = run_opts_of(c);   // every option and fact the schedule reads
+    const uint64_t parts[] = {(uint64_t)mode, (uint64_t)(uintptr_t)c->upm, (uint64_t)(uintptr_t)c->sk_parts, (uint64_t)c->num_sites,
                               (uint64_t)c->shard_cap, (uint64_t)(uintptr_t)c->recs, (uint64_t)(uintptr_t)c->sets,
                               (uint64_t)(uintptr_t)c->cmask, (uint64_t)(uintptr_t)c->root_final,
                               (uint64_t)(uintptr_t)c->leaf_planes, (uint64_t)(uintptr_t)c->leaf_present,
                               (uint64_t)(uintptr_t)c->leaf_flag, (uint64_t)(uintptr_t)c->cons,
                               (uint64_t)(uintptr_t)c->forced, (uint64_t)(uintptr_t)c->score,
                               (uint64_t)(uintptr_t)c->root_code, (uint64_t)(uintptr_t)c->shard_cnt,
-                              (uint64_t)(uintptr_t)c->sub_planes, (uint64_t)nt_policy(c),
+                              (uint64_t)(uintptr_t)c->sub_planes,
                               (uint64_t)(uintptr_t)c->dt.child_off, (uint64_t)(uintptr_t)c->stream};
     uint64_t h = 1469598103934665603ull;
+    const unsigned char* ob = reinterpret_cast<const unsigned char*>(&o);
+    for (size_t k = 0; k < sizeof(o); ++k) h = (h ^ ob[k]) * 1099511628211ull;
     for (uint64_t v : parts) h = (h ^ v) * 1099511628211ull;
     return h | 1;
 }
@@ -660,7 +649,6 @@ int pm_tree_upload(pm_ctx* c, const pm_tree* t) {
     const hipError_t e = upload_tree(p, c->stream, dt, tree_bytes);
     if (e != hipSuccess) return hip_fail(c, e, "tree upload");
     ClusterPlan& cl = p.ht.cl;
-    for (const NodeDesc& x : cl.items) cl.max_degree = std::max(cl.max_degree, x.e1 - x.e0);
     cl.items.clear();   // (device only)
     cl.items.shrink_to_fit();
     cl.down_items.clear();

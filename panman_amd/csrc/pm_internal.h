@@ -25,25 +25,16 @@
 #include <vector>
 
 #include "../../include/panman_gpu.h"
-#include "pm_plan.h"   // the planner's constants and records, HostTree, the phase log and host threads
+#include "pm_schedule.h"   // over pm_plan.h (the planner's constants and records, HostTree, the phase log and host threads): the launch schedule and the constants it reads
 
 namespace pm {
 
-constexpr int kWave = 64;
-constexpr int kWavesPerBlock = 4;
-constexpr int kBlock = kWave * kWavesPerBlock;
 #ifndef PM_SHARDS
 #define PM_SHARDS 1024
 #endif
 constexpr int kShards = PM_SHARDS;
 constexpr int kClasses = 6;   // post-order, pre-order levels, score, replay, whole graph, pre-order tail
-// Compact complex lanes (Fitch records, pm_kernels.h cx_store): a complex word stores its code
-// planes, its multi-code-site mask and up to kCxSets 16-bit sets (32 B) instead of 16 planes
-// (64 B); 0 = the 16-plane format.  Record quads per word: simple area + complex areas.
-#ifndef PM_CX_COMPACT
-#define PM_CX_COMPACT 0
-#endif
-constexpr bool kCxCompact = PM_CX_COMPACT != 0;
+// Record quads per word (kCxCompact: pm_schedule.h): simple area + complex areas.
 constexpr int kFitchRecQuads = kCxCompact ? 6 : 5;
 constexpr int kMaskWords = 8;     // record masks per (node, tile): complex, simple, dirty, parent's
                                   // complex, parent's simple, an S2 / S3 node's pushed dirty lanes,
@@ -153,7 +144,6 @@ struct pm_ctx {
     int64_t tail_pack_min_waves = 0;  // ... from this many (S item, tile) waves (0: kTailPackMinWaves, -1: always)
     bool down_pack = true;            // Fitch, all leaves present: large dense pre-order levels in groups per wave, live words gathered into full waves (PM_OPT_DOWN_PACK)
     int64_t down_pack_min_waves = 0;  // ... from this many (item, tile) waves (0: kDownPackMinWaves, -1: always)
-    std::vector<int32_t> down_pack_ranges;   // ... the last Fitch launch sequence's such levels, (first dense index, items) pairs -- taken, or with the option off the ones it would take
     bool plain_up = true;             // grouped subtree form: plain nodes in the lean post-order kernels (PM_OPT_PLAIN_UP)
     int64_t plain_min_waves = 0;      // ... from this many (node, tile) waves (0: kPlainMinWaves)
     bool cluster = true;              // Fitch subtree form: LDS-staged post-order sweeps above ht.cl.h0 (PM_OPT_CLUSTER)
@@ -208,7 +198,7 @@ struct pm_ctx {
     // hipGraph of one pm_run (PM_OPT_GRAPH): captured on first use, replayed while the
     // launch sequence and every buffer it touches stay the same (graph_key)
     bool use_graph = false;
-    int32_t nt_loads = -1;            // PM_OPT_NT_LOADS: -1 by level size (nt_policy), 0 off, 1 on
+    int32_t nt_loads = -1;            // PM_OPT_NT_LOADS: -1 by level size (RunPaths::nt), 0 off, 1 on
     hipGraphExec_t graph_exec = nullptr;
     uint64_t graph_key = 0;
 
@@ -255,10 +245,17 @@ void timer_begin(pm_ctx* c, int cls);
 void timer_end(pm_ctx* c, int cls);
 
 // kernel launchers (pm_fitch.hip / pm_sankoff.hip / pm_synth.hip)
-hipError_t launch_fitch(pm_ctx* c, bool block);
-hipError_t launch_sankoff(pm_ctx* c, bool block);
-hipError_t launch_fitch_nt(pm_ctx* c, bool block);     // non-temporal set-record loads
-hipError_t launch_sankoff_nt(pm_ctx* c, bool block);
+hipError_t launch_fitch(pm_ctx* c, const Schedule& s);
+hipError_t launch_sankoff(pm_ctx* c, const Schedule& s);
+hipError_t launch_fitch_nt(pm_ctx* c, const Schedule& s);     // non-temporal set-record loads
+hipError_t launch_sankoff_nt(pm_ctx* c, const Schedule& s);
+// What a run's launch sequence depends on besides the tree (schedule_run, graph_key_of).
+inline RunOpts run_opts_of(const pm_ctx* c) {   // (in RunOpts' field order)
+    return RunOpts{c->virtual_leaf_parents, c->subtree_form, c->narrow_max, c->group_waves, c->group_levels, c->up_group,
+                   c->sub_down, c->tail_pack, c->tail_pack_min_waves, c->down_pack, c->down_pack_min_waves, c->plain_up,
+                   c->plain_min_waves, c->cluster, c->nt_loads, c->leaves_all_present, c->has_forced,
+                   (c->words + kWave - 1) / kWave};
+}
 // Records of the last run, sorted by (node, site) on the device, copied to host `out`.
 // pm_warmup: one kernel of each code object looked up, so the object is loaded
 hipError_t warm_fitch();

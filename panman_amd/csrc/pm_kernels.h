@@ -10,7 +10,7 @@
 
 // Set-record load policy of this translation unit: pm_fitch.hip / pm_sankoff.hip build the
 // kernels with ordinary loads, pm_fitch_nt.hip / pm_sankoff_nt.hip with non-temporal ones
-// (PM_NT_LOADS), each copy in a namespace of its own; launch_all picks one per run (nt_policy).
+// (PM_NT_LOADS), each copy in a namespace of its own; launch_all picks one per run (RunPaths::nt).
 #ifndef PM_NT_LOADS
 #define PM_NT_LOADS 0
 #endif
@@ -30,9 +30,6 @@ enum class Mode { kFitch, kSankoff, kBlockFitch };
 // stream as whole rows (DRAM pages, TLB entries) instead of 1-KiB pieces of thousands of
 // rows.  One-wave kernels: wave g = (item g / tiles, tile g % tiles); one-workgroup
 // kernels: workgroup b likewise.  (PM_TILE_FAST=0: the former 2-D grid, tile = blockIdx.y.)
-#ifndef PM_TILE_FAST
-#define PM_TILE_FAST 1
-#endif
 __device__ __forceinline__ void wave_item(int wave, int32_t tiles, int32_t& item, int& tile) {
 #if PM_TILE_FAST
     const int32_t g = (int32_t)blockIdx.x * kWavesPerBlock + wave;
@@ -54,41 +51,12 @@ __device__ __forceinline__ void block_item(int32_t tiles, int32_t& item, int& ti
 #endif
 }
 
-// Grids of the level launches (count items x tiles; memory bounds count * tiles far below 2^31).
-inline dim3 wave_grid(int32_t count, int32_t tiles) {
-#if PM_TILE_FAST
-    return dim3((unsigned)(((int64_t)count * tiles + kWavesPerBlock - 1) / kWavesPerBlock));
-#else
-    return dim3((count + kWavesPerBlock - 1) / kWavesPerBlock, tiles);
-#endif
-}
-inline dim3 block_grid(int32_t count, int32_t tiles) {
-#if PM_TILE_FAST
-    return dim3((unsigned)((int64_t)count * tiles));
-#else
-    return dim3(count, tiles);
-#endif
-}
-
-// Levels holding nodes of both out-degree classes go to one mixed launch when the narrow
-// part is at most this many waves (the mixed kernel runs at the wide kernel's occupancy).
-#ifndef PM_MIXED_MAX_WAVES
-#define PM_MIXED_MAX_WAVES 4096
-#endif
-constexpr int64_t kMixedMaxWaves = PM_MIXED_MAX_WAVES;
+// (the level launches' grids, kMixedMaxWaves, kPlainMinWaves, kGroupLevels, kDownPack* and kTailPack*: pm_schedule.h)
 // Narrow-level band launches (PM_OPT_NARROW): one workgroup of 16 waves per tile.
 #ifndef PM_BAND_WAVES
 #define PM_BAND_WAVES 16
 #endif
 constexpr int kBandWaves = PM_BAND_WAVES;
-// Plain post-order prefixes (PM_OPT_PLAIN_UP) get a launch of their own only from this many
-// (node, tile) waves: the lean kernel's higher occupancy pays on levels that fill the chip
-// many times over, a second dependent launch costs more on smaller ones (C3 with a split at
-// every level: +0.2 ms).
-#ifndef PM_PLAIN_MIN_WAVES
-#define PM_PLAIN_MIN_WAVES 65536
-#endif
-constexpr int64_t kPlainMinWaves = PM_PLAIN_MIN_WAVES;
 constexpr int kBandBlock = kBandWaves * kWave;
 
 struct UpArgs {
@@ -1603,10 +1571,6 @@ __device__ __forceinline__ void resolve_final(const DownArgs& a, bool is_root, i
 // above it, starting from the last final stored before the launch (descriptor: pad0 =
 // grandparent, pad1 = great-grandparent; the fourth level's top ancestor's parent is one
 // scalar load beside the mask loads), so g + 1 levels cost one launch.
-#ifndef PM_GROUP_LEVELS
-#define PM_GROUP_LEVELS 4
-#endif
-constexpr int kGroupLevels = PM_GROUP_LEVELS;
 static_assert(kGroupLevels >= 2 && kGroupLevels <= 4, "level groups: 2 to 4 levels");
 template <Mode M, bool AP, bool SUB, bool GROUP = false>
 __device__ __forceinline__ void down_node(const DownArgs& a, const NodeDesc& d, int32_t n, uint32_t salt, int tile,
@@ -1743,20 +1707,11 @@ __device__ __forceinline__ uint32_t bits_below(uint64_t m, uint32_t l) {   // se
 //   lane, the parent's final, the children's dirty words -- and goes on as down_node does.
 // Same addresses as the items' own waves, live lanes only.  Never the root's level (its wave
 // writes root_final and the root codes at every lane).
-#ifndef PM_DOWN_PACK
-#define PM_DOWN_PACK 8
-#endif
-// (five waves per SIMD: 92 VGPRs, no scratch; at six the round's loads -- 4 + 16 + 4 + 16
+// (kDownPack, kDownPackMinWaves: pm_schedule.h; five waves per SIMD: 92 VGPRs, no scratch; at six the round's loads -- 4 + 16 + 4 + 16
 // registers in flight together -- spill 14 VGPRs)
 #ifndef PM_DOWN_PACK_WAVES
 #define PM_DOWN_PACK_WAVES 5
 #endif
-constexpr int kDownPack = PM_DOWN_PACK;
-// ... from this many (item, tile) waves of the level's own launch (the packed tail's threshold)
-#ifndef PM_DOWN_PACK_MIN_WAVES
-#define PM_DOWN_PACK_MIN_WAVES 65536
-#endif
-constexpr int64_t kDownPackMinWaves = PM_DOWN_PACK_MIN_WAVES;
 // per item: {parent, c0, c1, node id}, the children's leaves {l00, l01, l10, l11}, the first
 // child's ids, the second's, {x, s}, {px, ps}, {k0, k1}
 constexpr int kDownInfoQuads = 7;
@@ -1989,21 +1944,13 @@ __global__ __launch_bounds__(kBandBlock) void k_down_band(DownArgs a, const int3
 // Bytes and lines read are those of the items' own waves (same addresses, dirty lanes only).
 // G = 4, 8 and 16 measured alike at N* (k_tail 1.36 ms each, 2.17 ms unpacked); 8 keeps seven
 // waves per SIMD (68 VGPRs, 22 KiB of LDS per block), 16 would drop to five (28 KiB).
-#ifndef PM_TAIL_PACK
-#define PM_TAIL_PACK 8
-#endif
 #ifndef PM_TAIL_PACK_WAVES
 #define PM_TAIL_PACK_WAVES 6
 #endif
-constexpr int kTailPack = PM_TAIL_PACK;
-// ... from this many (S item, tile) waves of the unpacked launch: eight times the 8192 waves the
+// (kTailPack: pm_schedule.h) ... from kTailPackMinWaves (S item, tile) waves of the unpacked launch: eight times the 8192 waves the
 // chip holds.  A launch that fits the chip at once has every item's loads in flight together
 // already, and a group's rounds only run one behind the other (C2, a few thousand such waves:
 // 0.1838 -> 0.1857 ms per step packed; N*, about 3M: 14.16 -> 13.24 ms).
-#ifndef PM_TAIL_PACK_MIN_WAVES
-#define PM_TAIL_PACK_MIN_WAVES 65536
-#endif
-constexpr int64_t kTailPackMinWaves = PM_TAIL_PACK_MIN_WAVES;
 constexpr int kPackInfoQuads = 4;   // per item: {parent, enc, ix, iy}, id[0..3], {id[4], 0, 0, 0}, {px, ps}
 
 template <Mode M, int G>

@@ -193,9 +193,10 @@ int pm_design_bytes(pm_ctx* c, double* out, int n) {
     hipError_t e = hipMemcpyAsync(m.data(), c->cmask, m.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return hip_fail(c, e, "record masks");
-    const bool virt = c->virtual_leaf_parents;
-    const bool sub = virt && (mode == PM_MODE_FITCH || mode == PM_MODE_SANKOFF) && c->subtree_form && c->leaves_all_present &&
-                     ht.num_sshape > 0;
+    // the paths and the packed levels of the launch sequence (under the options as they stand)
+    const Schedule sched = schedule_run(ht, run_opts_of(c), mode);
+    const RunPaths& paths = sched.paths;
+    const bool virt = paths.virt, sub = paths.sub;
     const int32_t root = c->dt.root_dense;
     // virtual nodes as pm_tree_upload forms them (leaf-parents: not the root, one or two
     // children, all leaves; subtree form: S2 / S3 too): vnode = the leaves their parent reads
@@ -253,19 +254,17 @@ int pm_design_bytes(pm_ctx* c, double* out, int n) {
     // receives its parent's final (pre-order sweeps) through LDS
     // (post-order sweeps: Fitch, and Sankoff when they cover every height with <= 255-child
     // nodes, as launch_sankoff takes them; pre-order sweeps: both modes)
-    const bool planned = sub && c->cluster && ht.cl.band_wg.size() > 1 && !ht.cl.slot_of.empty();
-    const bool clu = planned && (mode == PM_MODE_FITCH || (ht.cl.h0 == 0 && ht.cl.max_degree <= 255));
-    auto in_cluster = [&](int32_t d) { return planned && ht.cl.slot_of[d] >= 0; };
-    auto in_lds = [&](int32_t d) { return clu && in_cluster(d); };
-    const bool down_lds = planned && ht.cl.down && (mode == PM_MODE_SANKOFF || !c->sub_down);
+    auto in_cluster = [&](int32_t d) { return paths.planned && !ht.cl.slot_of.empty() && ht.cl.slot_of[d] >= 0; };
+    auto in_lds = [&](int32_t d) { return paths.clu && in_cluster(d); };
+    const bool down_lds = paths.cld;
     // Packed levels (PM_OPT_DOWN_PACK, Fitch): in_pack marks the nodes of the levels the last
     // launch sequence packed -- or, the option off, would have packed.  Their live lanes
     // (down_packed) are counted for out[20..30]; with the option on the own simple codes and the
     // parent finals are read at live lanes only.
     std::vector<uint8_t> in_pack(I, 0), under_root(I, 0);
     if (mode == PM_MODE_FITCH)
-        for (size_t k = 0; k + 1 < c->down_pack_ranges.size(); k += 2)
-            for (int32_t i = 0; i < c->down_pack_ranges[k + 1]; ++i) in_pack[c->down_pack_ranges[k] + i] = 1;
+        for (size_t k = 0; k + 1 < sched.down_pack_ranges.size(); k += 2)
+            for (int32_t i = 0; i < sched.down_pack_ranges[k + 1]; ++i) in_pack[sched.down_pack_ranges[k] + i] = 1;
     for (int32_t k = ht.child_off[root]; k < ht.child_off[root + 1]; ++k)
         if (ht.child_enc[k] >= 0) under_root[ht.child_enc[k]] = 1;
     const bool packed_on = mode == PM_MODE_FITCH && c->down_pack;

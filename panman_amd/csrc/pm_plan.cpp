@@ -338,6 +338,7 @@ void subtree_form(const Topology& tp, TreePlan& p) {
 void plan_sweeps(TreePlan& p, int32_t max_level, bool chain, PhaseClock& clock) {
     ClusterPlan& cl = p.ht.cl;
     plan_clusters(p.ht, p.up_order_k, p.child_enc_k, p.parent_dense, p.vleaf, max_level, chain, cl);
+    for (const NodeDesc& x : cl.items) cl.max_degree = std::max(cl.max_degree, x.e1 - x.e0);   // (the schedule reads it: run_paths)
     tree_phase(clock, "clusters");
     // (counts: the sweeps' first level, bands, workgroups per tile, longest workgroup in rounds)
     phase_add("cluster.first_level", (double)cl.h0);

@@ -11,7 +11,7 @@
 // count, per code, the finite children that hold it optimal (bit-sliced counters, B bits
 // per code); Z0 = codes of maximum count, Z1 = codes of maximum - 1.  B is chosen per
 // node by out-degree class so binary nodes pay for 2-bit counters only.
-#include "pm_kernels.h"
+#include "pm_launch.h"
 
 #if PM_NT_LOADS   // (pm_sankoff_nt.hip: the same passes, non-temporal set-record loads)
 #define launch_sankoff launch_sankoff_nt
@@ -607,303 +607,76 @@ __global__ __launch_bounds__(kBlock) void k_sankoff_merge(UpArgs a, const uint32
 
 }  // namespace
 
-hipError_t launch_sankoff(pm_ctx* c, bool block) {
-    const HostTree& ht = c->ht;
-    const DevTree& dt = c->dt;
-    const int32_t tiles = (c->words + kWave - 1) / kWave;
-    const int64_t wpad = (int64_t)tiles * kWave;
-
-    // nucleotide Sankoff evaluates leaf-parents of one or two leaves inline, like Fitch, and
-    // with every leaf present the S2 / S3 subtrees too (subtree form: their Z0 in the parent's
-    // post-order wave, their finals and records in the tail)
-    const bool virt = !block && c->virtual_leaf_parents;
-    const bool sub = virt && c->subtree_form && c->leaves_all_present && ht.num_sshape > 0;
-    const bool grp = sub && c->up_group;   // grouped post-order launches (PM_OPT_UP_GROUP)
-    const int form = sub ? 2 : virt ? 1 : 0;
-    const int32_t* child_enc = sub ? dt.child_enc_k : virt ? dt.child_enc_v : dt.child_enc;
-    const NodeDesc* up_desc = grp ? dt.up_desc_gs : sub ? dt.up_desc_k : virt ? dt.up_desc_v : dt.up_desc;
-    const NodeDesc* down_desc = sub ? dt.down_desc_k : virt ? dt.down_desc_v : dt.down_desc;
-    const std::vector<int32_t>& class_off = grp ? ht.up_class_off_gs : sub ? ht.up_class_off_k
-                                          : virt ? ht.up_class_off_v : ht.up_class_off;
-    const std::vector<int32_t>& part_off = grp ? ht.part_off_gs : sub ? ht.part_off_k : virt ? ht.part_off_v : ht.part_off;
-    const PartDesc* parts = grp ? dt.part_desc_gs : sub ? dt.part_desc_k : virt ? dt.part_desc_v : dt.part_desc;
-    const std::vector<int32_t>& down_off = sub ? ht.down_level_off_k : virt ? ht.down_level_off_v : ht.down_level_off;
-    UpArgs up{};
-    up.child_off = dt.child_off;
-    up.child_enc = child_enc;
-    up.vleaf = reinterpret_cast<const int4*>(dt.vleaf);
-    up.leaf_flag = c->leaf_flag;
-    up.leaf_planes = c->leaf_planes;
-    up.leaf_present = c->leaf_present;
-    up.sets = reinterpret_cast<uint4*>(c->sets);
-    up.cmask = c->cmask;
-    up.cons = c->cons;
-    up.forced = nullptr;   // Sankoff forces the root in the backward pass only
-    up.absent_code0 = block;
-    up.all_present = c->leaves_all_present;
-    up.root_dense = dt.root_dense;
-    up.tiles = tiles;
-    up.wpad = wpad;
-    up.desc_all = up_desc;   // grouped launches: pad0 / pad1 index the whole array
-    // up slots: the subtree form's kernels (alloc_work sizes them for its up orders)
-    if (sub && c->upm == nullptr) return hipErrorInvalidValue;
-    up.upm = sub ? c->upm : nullptr;
-    up.pslot = grp ? dt.pslot_gs : dt.pslot_k;
-    // LDS-staged sweeps over every height (k_sankoff_up_cluster) when the plan covers the whole
-    // post-order and no swept node has more than 255 children; the level kernels otherwise
-    const ClusterPlan& clp = ht.cl;
-    const bool sk_clu = sub && c->cluster && clp.band_wg.size() > 1 && clp.h0 == 0 && clp.max_degree <= 255;
-    const int H = sk_clu ? 0 : (int)(grp ? ht.up_level_off_gs : sub ? ht.up_level_off_k : virt ? ht.up_level_off_v : ht.up_level_off).size() - 1;
-    if (sk_clu) {
-        const ClArgs ca0{dt.cl_items, dt.cl_wg_off, dt.cl_slot_of, dt.cl_pslot, clp.upm_base, 0};
-        for (size_t bnd = 0; bnd + 1 < clp.band_wg.size(); ++bnd) {
-            ClArgs ca = ca0;
-            ca.wg0 = clp.band_wg[bnd];
-            const int64_t nwg = clp.band_wg[bnd + 1] - ca.wg0;
-            if (nwg == 0) continue;
-            timer_begin(c, 0);
-            hipLaunchKernelGGL(k_sankoff_up_cluster, dim3((unsigned)(nwg * tiles)), dim3(kWave), 0, c->stream, up, ca);
-            timer_end(c, 0);
+// Executes the schedule's steps (pm_schedule.cpp decides them; the pre-order half: pm_launch.h).
+// Nucleotide Sankoff evaluates leaf-parents inline, like Fitch, and with every leaf present the S2 / S3 subtrees too (their Z0 in
+// the parent's post-order wave, their finals and records in the tail); it forces the root in the backward pass only (up.forced null).
+hipError_t launch_sankoff(pm_ctx* c, const Schedule& s) {
+    const RunPaths& p = s.paths;
+    const bool grp = p.grp, sub = p.sub, ap = p.ap;
+    const DevForm f = dev_form(c, p);
+    const dim3 kb(kBlock);
+    UpArgs up = fill_up_args(c, p, f);
+    up.absent_code0 = p.block;
+    hipError_t e = run_steps(c, s, 0, s.first_down, [&](const Step& st, hipStream_t q) {
+        const dim3 grid = step_grid(st, up.tiles);
+        UpArgs a = up;
+        a.desc = f.up_desc + st.first;
+        a.count = st.count;
+        switch (st.kind) {
+        case StepKind::kUpSweep: {   // one band of the LDS-staged sweeps (every height swept)
+            const ClArgs ca{c->dt.cl_items, c->dt.cl_wg_off, c->dt.cl_slot_of, c->dt.cl_pslot, c->ht.cl.upm_base, st.first};
+            hipLaunchKernelGGL(k_sankoff_up_cluster, dim3(st.grid_x), dim3(kWave), 0, q, up, ca);
+            break;
         }
-    }
-    // nodes [b, e) of one level with more than 255 children: parts, then the merge
-    auto launch_parts = [&](int32_t b, int32_t e, hipStream_t s) {
-        const int32_t p0 = part_off[b], np = part_off[e] - p0;
-        int32_t widest = 0;
-        for (int32_t i = b; i < e; ++i) widest = std::max(widest, ht.up_degree[grp ? 3 : form][i]);
-        UpArgs pa = up;
-        pa.desc = up_desc;   // parts name their node by its global up-order position
-        UpArgs mg = up;
-        mg.desc = up_desc + b;
-        mg.count = e - b;
-        const dim3 grid = wave_grid(mg.count, tiles);
-        timer_begin(c, 0);
-        hipLaunchKernelGGL(k_sankoff_part, wave_grid(np, tiles), dim3(kBlock), 0, s, pa, parts + p0, np, c->sk_parts);
-        if (widest < (1 << 16)) hipLaunchKernelGGL(k_sankoff_merge<16>, grid, dim3(kBlock), 0, s, mg, c->sk_parts);
-        else hipLaunchKernelGGL(k_sankoff_merge<32>, grid, dim3(kBlock), 0, s, mg, c->sk_parts);
-        timer_end(c, 0);
-    };
-    // runs of >= 2 narrow levels with only out-degree <= 3 nodes (PM_OPT_NARROW): one band each
-    auto narrow_up = [&](int h) {
-        const int32_t b = class_off[h * kDegreeClasses], m = class_off[h * kDegreeClasses + 1],
-                      e = class_off[(h + 1) * kDegreeClasses];
-        return e == m && m - b <= c->narrow_max;
-    };
-    for (int h = 0; h < H; ++h) {
-        if (c->narrow_max > 0 && narrow_up(h)) {
-            int h1 = h + 1;
-            while (h1 < H && narrow_up(h1)) ++h1;
-            if (h1 - h >= 2) {
-                up.desc = up_desc;
-                const int32_t* tab = dt.lvl + ht.lvl_up[grp ? 4 : form];
-                timer_begin(c, 0);
-                if (grp) hipLaunchKernelGGL((k_sankoff_up_band<true, true, true>), dim3(tiles), dim3(kBandBlock), 0, c->stream, up, tab, h, h1);
-                else if (sub) hipLaunchKernelGGL((k_sankoff_up_band<true, true>), dim3(tiles), dim3(kBandBlock), 0, c->stream, up, tab, h, h1);
-                else if (c->leaves_all_present) hipLaunchKernelGGL((k_sankoff_up_band<true>), dim3(tiles), dim3(kBandBlock), 0, c->stream, up, tab, h, h1);
-                else hipLaunchKernelGGL((k_sankoff_up_band<false>), dim3(tiles), dim3(kBandBlock), 0, c->stream, up, tab, h, h1);
-                timer_end(c, 0);
-                h = h1 - 1;
-                continue;
-            }
+        case StepKind::kUpBand: {   // a run of narrow levels of out-degree <= 3 nodes
+            a.desc = f.up_desc;
+            const dim3 tg(st.grid_x), tb(kBandBlock);
+            if (grp) hipLaunchKernelGGL((k_sankoff_up_band<true, true, true>), tg, tb, 0, q, a, f.lvl_up, st.h0, st.h1);
+            else if (sub) hipLaunchKernelGGL((k_sankoff_up_band<true, true>), tg, tb, 0, q, a, f.lvl_up, st.h0, st.h1);
+            else if (ap) hipLaunchKernelGGL((k_sankoff_up_band<true>), tg, tb, 0, q, a, f.lvl_up, st.h0, st.h1);
+            else hipLaunchKernelGGL((k_sankoff_up_band<false>), tg, tb, 0, q, a, f.lvl_up, st.h0, st.h1);
+            break;
         }
-        {   // a small level with narrow and wide (<= 255 children) nodes: one launch
-            const int32_t b = class_off[h * kDegreeClasses], m = class_off[h * kDegreeClasses + 1],
-                          w4 = class_off[h * kDegreeClasses + 2], w8 = class_off[h * kDegreeClasses + 3];
-            if (m > b && w8 > m && (int64_t)(m - b) * tiles <= kMixedMaxWaves) {
-                up.desc = up_desc + b;
-                up.count = m - b;
-                const int32_t nb = (int32_t)wave_grid(up.count, tiles).x;
-                const dim3 grid((unsigned)(nb + (int64_t)(w8 - m) * tiles));
-                timer_begin(c, 0);
-                if (w8 > w4 && grp) hipLaunchKernelGGL((k_sankoff_up_mixed<8, true, true, true>), grid, dim3(kBlock), 0, c->stream, up, up_desc + m, nb);
-                else if (grp) hipLaunchKernelGGL((k_sankoff_up_mixed<4, true, true, true>), grid, dim3(kBlock), 0, c->stream, up, up_desc + m, nb);
-                else if (w8 > w4 && sub) hipLaunchKernelGGL((k_sankoff_up_mixed<8, true, true>), grid, dim3(kBlock), 0, c->stream, up, up_desc + m, nb);
-                else if (sub) hipLaunchKernelGGL((k_sankoff_up_mixed<4, true, true>), grid, dim3(kBlock), 0, c->stream, up, up_desc + m, nb);
-                else if (w8 > w4 && c->leaves_all_present) hipLaunchKernelGGL((k_sankoff_up_mixed<8, true>), grid, dim3(kBlock), 0, c->stream, up, up_desc + m, nb);
-                else if (w8 > w4) hipLaunchKernelGGL((k_sankoff_up_mixed<8, false>), grid, dim3(kBlock), 0, c->stream, up, up_desc + m, nb);
-                else if (c->leaves_all_present) hipLaunchKernelGGL((k_sankoff_up_mixed<4, true>), grid, dim3(kBlock), 0, c->stream, up, up_desc + m, nb);
-                else hipLaunchKernelGGL((k_sankoff_up_mixed<4, false>), grid, dim3(kBlock), 0, c->stream, up, up_desc + m, nb);
-                timer_end(c, 0);
-                // the level's nodes above 255 children (if any) still go to the parts below
-                for (int k = 3; k < kDegreeClasses; ++k) {
-                    const int32_t pb = class_off[h * kDegreeClasses + k], pe = class_off[h * kDegreeClasses + k + 1];
-                    if (pe > pb) launch_parts(pb, pe, c->stream);
-                }
-                continue;
-            }
+        case StepKind::kUpMixed: {   // a small level's narrow and wide (<= 255 children) nodes in one launch
+            const dim3 mg(st.grid_x);
+            const NodeDesc* wdesc = a.desc + st.count;
+            const int32_t nb = (int32_t)wave_grid_x(st.count, up.tiles);
+            const bool w8 = st.variant == 8;
+            if (w8 && grp) hipLaunchKernelGGL((k_sankoff_up_mixed<8, true, true, true>), mg, kb, 0, q, a, wdesc, nb);
+            else if (grp) hipLaunchKernelGGL((k_sankoff_up_mixed<4, true, true, true>), mg, kb, 0, q, a, wdesc, nb);
+            else if (w8 && sub) hipLaunchKernelGGL((k_sankoff_up_mixed<8, true, true>), mg, kb, 0, q, a, wdesc, nb);
+            else if (sub) hipLaunchKernelGGL((k_sankoff_up_mixed<4, true, true>), mg, kb, 0, q, a, wdesc, nb);
+            else if (w8 && ap) hipLaunchKernelGGL((k_sankoff_up_mixed<8, true>), mg, kb, 0, q, a, wdesc, nb);
+            else if (w8) hipLaunchKernelGGL((k_sankoff_up_mixed<8, false>), mg, kb, 0, q, a, wdesc, nb);
+            else if (ap) hipLaunchKernelGGL((k_sankoff_up_mixed<4, true>), mg, kb, 0, q, a, wdesc, nb);
+            else hipLaunchKernelGGL((k_sankoff_up_mixed<4, false>), mg, kb, 0, q, a, wdesc, nb);
+            break;
         }
-        // the level's degree classes are independent: the wide ones run on the side stream,
-        // beside the narrow launch (parallel graph branches), when both kinds are present
-        const int32_t lb = class_off[h * kDegreeClasses], lm = class_off[h * kDegreeClasses + 1],
-                      le = class_off[(h + 1) * kDegreeClasses];
-        const bool fork = lm > lb && le > lm;
-        if (fork) {
-            const hipError_t fe = side_fork(c);
-            if (fe != hipSuccess) return fe;
+        case StepKind::kUpNarrow:   // out-degree <= 3: one wave per (node, tile)
+            if (st.variant == kNarrowPlain) hipLaunchKernelGGL((k_sankoff_up<2, true, true, false, true>), grid, kb, 0, q, a);
+            else if (st.variant == kNarrowRecomp) hipLaunchKernelGGL((k_sankoff_up<2, true, true, true>), grid, kb, 0, q, a);
+            else if (sub) hipLaunchKernelGGL((k_sankoff_up<2, true, true>), grid, kb, 0, q, a);
+            else if (ap) hipLaunchKernelGGL((k_sankoff_up<2, true>), grid, kb, 0, q, a);
+            else hipLaunchKernelGGL((k_sankoff_up<2, false>), grid, kb, 0, q, a);
+            break;
+        case StepKind::kUpWide:   // <= 15 / <= 255 children: one workgroup per (node, tile), 4- / 8-bit counters
+            if (st.variant == 4) hipLaunchKernelGGL(k_sankoff_up_wide<4>, grid, kb, 0, q, a);
+            else hipLaunchKernelGGL(k_sankoff_up_wide<8>, grid, kb, 0, q, a);
+            break;
+        case StepKind::kUpParts:   // more than 255 children: parts, which name their node by its up-order position
+            a.desc = f.up_desc;
+            hipLaunchKernelGGL(k_sankoff_part, grid, kb, 0, q, a, f.parts + st.first, st.count, c->sk_parts);
+            break;
+        case StepKind::kUpMerge:   // ... then the merge, by the widest node's counter width
+            if (st.variant == 16) hipLaunchKernelGGL(k_sankoff_merge<16>, grid, kb, 0, q, a, c->sk_parts);
+            else hipLaunchKernelGGL(k_sankoff_merge<32>, grid, kb, 0, q, a, c->sk_parts);
+            break;
+        default:
+            break;
         }
-        for (int k = kDegreeClasses - 1; k >= 0; --k) {   // wide classes first: they go to the side
-            const int32_t b = class_off[h * kDegreeClasses + k];
-            const int32_t e = class_off[h * kDegreeClasses + k + 1];
-            if (e == b) continue;
-            hipStream_t s = fork && k > 0 ? c->side : c->stream;
-            // the grouped order's plain prefix of the narrow class: the lean kernel first
-            int32_t np = k == 0 && grp && c->plain_up ? std::min(ht.up_plain_gs[h], e - b) : 0;
-            if ((int64_t)np * tiles < (c->plain_min_waves > 0 ? c->plain_min_waves : kPlainMinWaves)) np = 0;
-            if (np > 0) {
-                up.desc = up_desc + b;
-                up.count = np;
-                timer_begin(c, 0);
-                hipLaunchKernelGGL((k_sankoff_up<2, true, true, false, true>), wave_grid(np, tiles), dim3(kBlock), 0, s, up);
-                timer_end(c, 0);
-                if (np == e - b) continue;
-            }
-            up.desc = up_desc + b + np;
-            up.count = e - b - np;
-            const dim3 grid = wave_grid(up.count, tiles), wide = block_grid(up.count, tiles);
-            timer_begin(c, 0);
-            if (k == 0 && grp && ht.up_recomp_gs[h]) hipLaunchKernelGGL((k_sankoff_up<2, true, true, true>), grid, dim3(kBlock), 0, s, up);
-            else if (k == 0 && sub) hipLaunchKernelGGL((k_sankoff_up<2, true, true>), grid, dim3(kBlock), 0, s, up);
-            else if (k == 0 && c->leaves_all_present) hipLaunchKernelGGL((k_sankoff_up<2, true>), grid, dim3(kBlock), 0, s, up);
-            else if (k == 0) hipLaunchKernelGGL((k_sankoff_up<2, false>), grid, dim3(kBlock), 0, s, up);
-            else if (k == 1) hipLaunchKernelGGL(k_sankoff_up_wide<4>, wide, dim3(kBlock), 0, s, up);
-            else if (k == 2) hipLaunchKernelGGL(k_sankoff_up_wide<8>, wide, dim3(kBlock), 0, s, up);
-            else {   // more than 255 children: parts, then the merge
-                timer_end(c, 0);
-                launch_parts(b, e, s);
-                continue;
-            }
-            timer_end(c, 0);
-        }
-        if (fork) {
-            const hipError_t je = side_join(c);
-            if (je != hipSuccess) return je;
-        }
-    }
-
-    hipError_t err = hipMemsetAsync(c->shard_cnt, 0, sizeof(uint32_t) * kShards, c->stream);
-    if (err != hipSuccess) return err;
-    DownArgs dn{};
-    dn.child_off = dt.child_off;
-    dn.child_enc = child_enc;
-    dn.parent_dense = dt.parent_dense;
-    dn.internal_id = dt.internal_id;
-    dn.leaf_id = dt.leaf_id;
-    dn.leaf_flag = c->leaf_flag;
-    dn.leaf_planes = c->leaf_planes;
-    dn.leaf_present = c->leaf_present;
-    dn.sets = reinterpret_cast<uint4*>(c->sets);
-    dn.cmask = c->cmask;
-    dn.root_final = c->root_final;
-    dn.dense_base = -1;
-    dn.cons = c->cons;
-    dn.root_dense = dt.root_dense;
-    dn.tiles = tiles;
-    dn.wpad = wpad;
-    dn.words = c->words;
-    dn.sites = c->num_sites;
-    dn.recs = c->recs;
-    dn.shard_cap = c->shard_cap;
-    dn.shard_cnt = c->shard_cnt;
-    dn.root_code = c->root_code;
-    dn.forced = c->has_forced ? c->forced : nullptr;
-    dn.absent_code0 = block;
-    dn.all_present = c->leaves_all_present;
-    dn.vleaf = reinterpret_cast<const int4*>(dt.vleaf);
-    dn.vinner = dt.vinner;
-    // pre-order sweeps over the planner's clusters (PM_OPT_CLUSTER, every level swept: the
-    // same schedule as the Fitch pre-order's, k_down_cluster<Sankoff>), the bands top-down
-    const ClusterPlan& cl = ht.cl;
-    const bool cld = sub && c->cluster && cl.band_wg.size() > 1 && cl.down;
-    if (cld) {
-        for (size_t bnd = cl.band_wg.size() - 1; bnd-- > 0;) {
-            const ClDownArgs ca{dt.cl_down_items, dt.cl_wg_off, cl.band_wg[bnd]};
-            const int64_t nwg = cl.band_wg[bnd + 1] - ca.wg0;
-            if (nwg == 0) continue;
-            timer_begin(c, 1);
-            hipLaunchKernelGGL(k_down_cluster<Mode::kSankoff>, dim3((unsigned)(nwg * tiles)), dim3(kWave), 0, c->stream, dn, ca);
-            timer_end(c, 1);
-        }
-    }
-    const int D = cld ? 0 : (int)down_off.size() - 1;
-    // a pre-order level = one range of dense indices: [down_off[d], down_off[d+1]) in the
-    // leaf-parent form, from down_dense_base_k[d] in the subtree form
-    const bool dense_all = sub ? ht.down_dense_k : virt && ht.down_dense_v;
-    auto dense_base_of = [&](int l) { return !dense_all ? -1 : sub ? ht.down_dense_base_k[l] : down_off[l]; };
-    for (int d = 0; d < D; ++d) {
-        if (c->narrow_max > 0 && down_off[d + 1] - down_off[d] <= c->narrow_max) {   // PM_OPT_NARROW
-            int d1 = d + 1;
-            while (d1 < D && down_off[d1 + 1] - down_off[d1] <= c->narrow_max) ++d1;
-            if (d1 - d >= 2) {
-                dn.desc = down_desc;
-                const int32_t* tab = dt.lvl + ht.lvl_down[form];
-                const int32_t* base = !dense_all ? nullptr : sub ? dt.lvl + ht.lvl_base_k : tab;
-                timer_begin(c, 1);
-                const bool grp = c->group_waves > 0;   // level groups inside the band
-                if (c->leaves_all_present && grp) hipLaunchKernelGGL((k_down_band<Mode::kSankoff, true, false, true>), dim3(tiles), dim3(kBandBlock), 0, c->stream, dn, tab, base, d, d1);
-                else if (c->leaves_all_present) hipLaunchKernelGGL((k_down_band<Mode::kSankoff, true>), dim3(tiles), dim3(kBandBlock), 0, c->stream, dn, tab, base, d, d1);
-                else if (grp) hipLaunchKernelGGL((k_down_band<Mode::kSankoff, false, false, true>), dim3(tiles), dim3(kBandBlock), 0, c->stream, dn, tab, base, d, d1);
-                else hipLaunchKernelGGL((k_down_band<Mode::kSankoff, false>), dim3(tiles), dim3(kBandBlock), 0, c->stream, dn, tab, base, d, d1);
-                timer_end(c, 1);
-                d = d1 - 1;
-                continue;
-            }
-        }
-        dn.desc = down_desc + down_off[d];
-        dn.count = down_off[d + 1] - down_off[d];
-        if (dn.count == 0) continue;
-        const bool dense = dense_all;
-        dn.dense_base = dense_base_of(d);
-        // levels d .. d + g - 1 in one launch (PM_OPT_GROUP_*; see launch_fitch)
-        auto narrow_down = [&](int l) { return c->narrow_max > 0 && down_off[l + 1] - down_off[l] <= c->narrow_max; };
-        auto band_at = [&](int l) { return narrow_down(l) && l + 1 < D && narrow_down(l + 1); };
-        int g = 1;
-        int64_t items = dn.count;
-        while (c->group_waves > 0 && g < std::min(c->group_levels, kGroupLevels) && d + g < D) {
-            const int32_t ng = down_off[d + g + 1] - down_off[d + g];
-            if (ng == 0 || (items + ng) * tiles > c->group_waves || band_at(d + g)) break;
-            items += ng;
-            ++g;
-        }
-        if (g > 1) {
-            for (int k = 0; k < 4; ++k) {
-                const int l = std::min(d + k, d + g - 1);
-                if (k > 0) dn.split[k - 1] = k < g ? down_off[d + k] - down_off[d] : (int32_t)items;
-                dn.dense_g[k] = dense_base_of(l);
-            }
-            dn.count = (int32_t)items;
-            const dim3 grid = wave_grid(dn.count, tiles);
-            timer_begin(c, 1);
-            if (c->leaves_all_present && dense) hipLaunchKernelGGL((k_down<Mode::kSankoff, true, true, false, true>), grid, dim3(kBlock), 0, c->stream, dn);
-            else if (c->leaves_all_present) hipLaunchKernelGGL((k_down<Mode::kSankoff, true, false, false, true>), grid, dim3(kBlock), 0, c->stream, dn);
-            else hipLaunchKernelGGL((k_down<Mode::kSankoff, false, false, false, true>), grid, dim3(kBlock), 0, c->stream, dn);
-            timer_end(c, 1);
-            d += g - 1;
-            continue;
-        }
-        const dim3 grid = wave_grid(dn.count, tiles);
-        timer_begin(c, 1);
-        if (c->leaves_all_present && dense) hipLaunchKernelGGL((k_down<Mode::kSankoff, true, true>), grid, dim3(kBlock), 0, c->stream, dn);
-        else if (c->leaves_all_present) hipLaunchKernelGGL((k_down<Mode::kSankoff, true, false>), grid, dim3(kBlock), 0, c->stream, dn);
-        else hipLaunchKernelGGL((k_down<Mode::kSankoff, false, false>), grid, dim3(kBlock), 0, c->stream, dn);
-        timer_end(c, 1);
-    }
-    // children beyond a node's second: one flat launch after the levels (k_tail)
-    const int32_t tail_total = sub ? ht.num_tail_k : virt ? ht.num_tail_v : ht.num_tail;
-    if (tail_total > 0) {
-        DownArgs t = dn;
-        t.tail = sub ? dt.tail_desc_k : virt ? dt.tail_desc_v : dt.tail_desc;
-        t.count = tail_total;
-        t.num_s = sub ? ht.num_tail_s : 0;
-        t.sbase = ht.sbase;
-        t.sub_planes = c->sub_planes;
-        const dim3 grid = wave_grid(t.count, tiles);
-        timer_begin(c, 5);
-        if (sub) hipLaunchKernelGGL((k_tail<Mode::kSankoff, true, true>), grid, dim3(kBlock), 0, c->stream, t);
-        else if (c->leaves_all_present) hipLaunchKernelGGL((k_tail<Mode::kSankoff, true>), grid, dim3(kBlock), 0, c->stream, t);
-        else hipLaunchKernelGGL((k_tail<Mode::kSankoff, false>), grid, dim3(kBlock), 0, c->stream, t);
-        timer_end(c, 5);
-    }
-    return hipGetLastError();
+    });
+    if (e == hipSuccess) e = run_down<false>(c, s, f, c->has_forced ? c->forced : nullptr, p.block);
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 // This file's code object, loaded ahead of its first launch (pm_warmup).

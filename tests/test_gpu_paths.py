@@ -1,6 +1,8 @@
 """The subtree form (every leaf present) against the oracle at the degree, band and option edges
-the launchers branch on (launch_fitch / launch_sankoff: sub, grp, clu / sk_clu, cld, sub_down,
-narrow bands, level groups, the non-temporal build, the four out-degree classes), on the
+the launch schedule branches on (run_paths / schedule_run in pm_schedule.cpp, executed by
+launch_fitch / launch_sankoff: sub, grp, clu -- Sankoff's with h0 == 0 and no node above 255
+children, "sk_clu" below -- cld, sub_down, narrow bands, level groups, the non-temporal build,
+the four out-degree classes), on the
 deterministic trees and mixed-class columns of _shapes.py.  Every comparison is bit-exact:
 records, root codes and score == records per site; every case reads the path it means to take
 off phase_report()."""
