@@ -174,6 +174,11 @@ int pm_set_stream(pm_ctx* ctx, void* hip_stream);
  *                  cut the nodes in id order into batches by the bytes of their entry records plus the
  *                  worst-case text (a node above the limit runs alone) and stream the text batch by
  *                  batch.  The text does not depend on it.
+ *   PM_OPT_REROOT_CHUNK_SITES (default 0, or 1 .. 2^24 - 4096): pm_reroot runs the nucleotide Fitch over the
+ *                  canonical columns in chunks.  0 sizes a chunk from the tree alone (at least 65536 columns, at
+ *                  most 2^24 - 4096, as many as fit 24 GiB of sets, finals and codes); another value is the
+ *                  chunk, capped by that size.  Odd values are allowed: a chunk may start on an odd column.  The
+ *                  result does not depend on it.
  * (Option ids 1, 4, 5 and 11 -- subtree-region, heavy-path-chain and level-band schedules,
  * tail records overlapped with the pre-order levels -- were measured slower than, or no
  * faster than, the level kernels on MI355X and removed.) */
@@ -198,6 +203,7 @@ int pm_set_stream(pm_ctx* ctx, void* hip_stream);
 #define PM_OPT_SUBNET_BATCH_ENTRIES 24
 #define PM_OPT_AA_BATCH_BYTES 25
 #define PM_OPT_MUTATIONS_BATCH_BYTES 26
+#define PM_OPT_REROOT_CHUNK_SITES 27
 int pm_set_option(pm_ctx* ctx, int option, int64_t value);
 /* Accumulate per-kernel-class device time with HIP events (see pm_kernel_times). */
 int pm_set_profiling(pm_ctx* ctx, int enable);
@@ -694,7 +700,12 @@ int pm_panman_write(const char* path, const pm_panmat* const* trees, int count, 
  * the reference rebuilds the secondary blocks' own sequences and block states
  * (src/reroot.cpp:55-89, src/panman.cpp:4722-4890), a second block level this layout does
  * not hold -- although pm_fasta, like printFASTAUltraFastHelper, replays such a PanMAT (the
- * mutation lands on the primary block). */
+ * mutation lands on the primary block).  A branch length that moves to another node (the
+ * leaf's, and that of every node between it and the old root) loses its fraction, as
+ * transform's `size_t oldBranchLen` makes it (:5855, :5888); a negative one is kept.  An old
+ * root left without a child (a unary root above the leaf's chain) returns
+ * PM_ERR_UNSUPPORTED: the reference reads children[0] of an empty list there (:5837).  The
+ * nucleotide Fitch runs in column chunks (PM_OPT_REROOT_CHUNK_SITES). */
 int pm_reroot(pm_ctx* ctx, const pm_panmat* tree, const char* leaf, pm_panman** out);
 
 /* Drop-in for Tree::subtreeExtractParallel(ids, {}) (src/subnet.cpp:3-135; the --subnet command,

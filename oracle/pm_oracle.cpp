@@ -1267,6 +1267,10 @@ bool sequence_from_reference(RTree& t, RNode* ref, Seq& seq, std::vector<bool>& 
     return true;
 }
 
+// `size_t oldBranchLen = node->branchLength` (src/panman.cpp:5855, :5888): a moved length loses its
+// fraction.  Undefined for a negative length, which is kept.
+float moved_len(float len) { return len >= 0 ? (float)(size_t)len : len; }
+
 // transformHelper (src/panman.cpp:5831-5865)
 RNode* transform_helper(RTree& t, RNode* node, bool& ok) {
     if (node == t.root) {
@@ -1284,7 +1288,7 @@ RNode* transform_helper(RTree& t, RNode* node, bool& ok) {
     RNode* par = node->parent;
     par->children.erase(std::find(par->children.begin(), par->children.end(), node));
     node->parent = nullptr;
-    const float old = node->len;
+    const float old = moved_len(node->len);
     node->len = 0;
     RNode* c = transform_helper(t, par, ok);
     node->children.push_back(c);
@@ -1300,7 +1304,7 @@ bool transform(RTree& t, RNode* node) {
     if (par == t.root) { node->len = 0; return true; }
     par->children.erase(std::find(par->children.begin(), par->children.end(), node));
     node->parent = nullptr;
-    const float old = node->len;
+    const float old = moved_len(node->len);
     auto nr = std::make_unique<RNode>();
     nr->id = "node_" + std::to_string(++t.internal_counter);
     nr->len = 0;

@@ -583,6 +583,11 @@ int pm_set_option(pm_ctx* c, int option, int64_t value) {
         c->subnet_batch_entries = value;
         return PM_OK;
     }
+    if (option == PM_OPT_REROOT_CHUNK_SITES) {
+        if (value < 0 || value > kMaxRerootChunk) return fail(c, PM_ERR_ARG, "PM_OPT_REROOT_CHUNK_SITES: 0 (by the tree's size) or 1 .. 2^24 - 4096 columns");
+        c->reroot_chunk_sites = value;
+        return PM_OK;
+    }
     if (option == PM_OPT_GROUP_WAVES) {
         if (value < 0) return fail(c, PM_ERR_ARG, "PM_OPT_GROUP_WAVES: >= 0 waves");
         c->group_waves = value;

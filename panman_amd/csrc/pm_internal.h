@@ -41,6 +41,8 @@ constexpr int kMaskWords = 8;     // record masks per (node, tile): complex, sim
                                   // Fitch: the first / second child's dirty lanes (one 64-B line)
 // The most sites one leaf upload takes (a record's site field is 24 bits; pm_leaves_upload).
 constexpr int64_t kMaxUploadSites = ((int64_t)1 << 24) - 1;
+// The most canonical columns pm_reroot hands the nucleotide Fitch at once (PM_OPT_REROOT_CHUNK_SITES).
+constexpr int64_t kMaxRerootChunk = ((int64_t)1 << 24) - 4096;
 // pm_subnet's default batch (PM_OPT_SUBNET_BATCH_ENTRIES), in expanded bases.  hipCUB takes its item count as an
 // int, so a batch must stay below 2^31; a base costs about 110 B of device memory across the pipeline (two
 // 8-B key and two 8-B value buffers, 12 B of coordinates, 9 B of fold results, then up to 33 B per survivor and
@@ -227,6 +229,7 @@ struct pm_ctx {
     int64_t aa_batch_bytes = (int64_t)1 << 30;    // pm_aa: codon tables and text per device batch of nodes (PM_OPT_AA_BATCH_BYTES)
     int64_t mutations_batch_bytes = (int64_t)1 << 30;   // pm_print_mutations: entry records and text per device batch of nodes (PM_OPT_MUTATIONS_BATCH_BYTES)
     int64_t subnet_batch_entries = pm::kSubnetBatchEntries;   // pm_subnet: expanded bases sorted per batch (PM_OPT_SUBNET_BATCH_ENTRIES)
+    int64_t reroot_chunk_sites = 0;               // pm_reroot: canonical columns per Fitch chunk, 0 = by the tree's size (PM_OPT_REROOT_CHUNK_SITES)
 };
 
 namespace pm {

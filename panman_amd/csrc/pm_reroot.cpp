@@ -7,7 +7,7 @@
 //      to the new root's block state, root parent state 1;
 //   4. nucleotide Fitch per canonical column (main positions and gap slots,
 //      src/reroot.cpp:130-226): the rows are converted to packed codes on the device
-//      ('-' and 'x' are state 1) and fed to the Fitch kernels in column chunks with the root
+//      ('-' and 'x' are state 1) and fed to the Fitch kernels in column chunks (PM_OPT_REROOT_CHUNK_SITES) with the root
 //      forced to the new root's characters; the root's parent state is the block
 //      consensus for main columns and a gap for gap slots;
 //   5. grouping into NucMut runs (src/reroot.cpp:228-262) on the host.
@@ -35,6 +35,11 @@ struct Shape {   // the reference's in-memory tree after transform, indexed by o
     int32_t root = -1;
 };
 
+// A branch length that moves to another node passes through `size_t oldBranchLen`
+// (src/panman.cpp:5855, :5862, :5888, :5900): 3.25 arrives as 3, 0.875 as 0.  That conversion is
+// undefined for a negative length, which is kept as it is.
+inline float moved_len(float len) { return len >= 0 ? (float)(size_t)len : len; }
+
 // transform(leaf) and transformHelper (src/panman.cpp:5831-5906), iteratively.
 bool transform(Shape& t, int32_t leaf, int64_t internal_nodes, std::string& err) {
     const int32_t par = t.parent[leaf];
@@ -49,7 +54,7 @@ bool transform(Shape& t, int32_t leaf, int64_t internal_nodes, std::string& err)
     };
     erase(par, leaf);
     t.parent[leaf] = -1;
-    const float leaf_len = t.len[leaf];
+    const float leaf_len = moved_len(t.len[leaf]);
     const int32_t nr = (int32_t)t.name.size();
     t.name.push_back("node_" + std::to_string(internal_nodes + 1));   // newInternalNodeId()
     t.kids.push_back({leaf});
@@ -66,7 +71,7 @@ bool transform(Shape& t, int32_t leaf, int64_t internal_nodes, std::string& err)
     for (size_t j = 0; j < k; ++j) {
         erase(chain[j + 1], chain[j]);
         t.parent[chain[j]] = -1;
-        old_len[j] = t.len[chain[j]];
+        old_len[j] = moved_len(t.len[chain[j]]);
         t.len[chain[j]] = 0;
     }
     int32_t top;   // what helper(old root) returns
@@ -214,7 +219,8 @@ int reroot(pm_ctx* c, const pm_panmat* p, const std::string& leaf_name, PanmanTr
     if (e != hipSuccess) return hip_fail(c, e, "root row download");
     const int64_t budget = (int64_t)24 << 30;   // device bytes for sets / finals / codes per chunk
     const int64_t per_col = 3 * (int64_t)M + L + 64;
-    const int64_t chunk = std::max<int64_t>(1 << 16, std::min<int64_t>(((int64_t)1 << 24) - 4096, budget / per_col));
+    int64_t chunk = std::max<int64_t>(1 << 16, std::min<int64_t>(kMaxRerootChunk, budget / per_col));
+    if (c->reroot_chunk_sites > 0) chunk = std::min(chunk, c->reroot_chunk_sites);   // PM_OPT_REROOT_CHUNK_SITES
     const int64_t cstride = (std::min(chunk, C) + 1) / 2 + 15 & ~(int64_t)15;
     Dev<uint8_t> d_codes;
     if (d_codes.alloc((size_t)std::max(L, 1) * cstride, false, c->stream) != hipSuccess) return fail(c, PM_ERR_OOM, "reroot code staging");
