@@ -179,6 +179,10 @@ int pm_set_stream(pm_ctx* ctx, void* hip_stream);
  *                  most 2^24 - 4096, as many as fit 24 GiB of sets, finals and codes); another value is the
  *                  chunk, capped by that size.  Odd values are allowed: a chunk may start on an odd column.  The
  *                  result does not depend on it.
+ *   PM_OPT_USHER_BATCH_BYTES (default 1 GiB, at least 4096): pm_to_usher / pm_to_usher_fd cut the nodes in
+ *                  pre-order into batches by the bytes of their entry records, sort keys and worst-case
+ *                  output (a node above the limit runs alone) and stream the bytes batch by batch.  The
+ *                  bytes do not depend on it.
  * (Option ids 1, 4, 5 and 11 -- subtree-region, heavy-path-chain and level-band schedules,
  * tail records overlapped with the pre-order levels -- were measured slower than, or no
  * faster than, the level kernels on MI355X and removed.) */
@@ -204,6 +208,7 @@ int pm_set_stream(pm_ctx* ctx, void* hip_stream);
 #define PM_OPT_AA_BATCH_BYTES 25
 #define PM_OPT_MUTATIONS_BATCH_BYTES 26
 #define PM_OPT_REROOT_CHUNK_SITES 27
+#define PM_OPT_USHER_BATCH_BYTES 28
 int pm_set_option(pm_ctx* ctx, int option, int64_t value);
 /* Accumulate per-kernel-class device time with HIP events (see pm_kernel_times). */
 int pm_set_profiling(pm_ctx* ctx, int enable);
@@ -661,6 +666,66 @@ int pm_aa_fd(pm_ctx* ctx, const pm_panmat* panmat, int64_t start, int64_t end, i
  * `odd_substitutions` nullable).  A failed write: PM_ERR_ARG (errno kept), as pm_fasta_fd. */
 int pm_print_mutations(pm_ctx* ctx, const pm_panmat* panmat, char** text, int64_t* length, int64_t* odd_substitutions);
 int pm_print_mutations_fd(pm_ctx* ctx, const pm_panmat* panmat, int fd, int64_t* length, int64_t* odd_substitutions);
+/* Drop-in for panmanToUsher (src/panman2usher.cpp:564-604, the walk getNodeDFS at :282-562; the
+ * --toUsher command, src/panmanUtils.cpp:1205-1240): the tree as an UShER mutation-annotated tree, a
+ * Parsimony::data Protobuf message (usher.proto) of the Newick string and one mutation_list per node.
+ * THE REFERENCE IS UNDEFINED AS WRITTEN: panmanToUsher indexes globalCoords_t and pseudoRoot while both
+ * are still empty vectors (:565-569, used at :18 and :69).  What is restated here is what its code does
+ * with both sized to the largest block id + 1.  Cells, positions 0..n_b, gap slots and nucleotide codes
+ * are those of pm_print_mutations above.
+ *   position      (getCoordMap, :3-51) the cells of a block are, per position 0..n_b, its gap slots
+ *                 ascending and then its main character; position(cell) = 1 + the cells before it over
+ *                 the blocks in ascending id (an id without a block has no cell).  That is the canonical
+ *                 aligned column + 1.
+ *   pseudo-root   (getPseudoRoot, :53-90) the consensus character at every main cell, '-' in every gap
+ *                 slot, 'x' at the sentinel.
+ *   the walk      (getNodeDFS) depth-first pre-order, children in stored order, the root included; every
+ *                 node gives one mutation_list, possibly empty.  The running sequence starts as the
+ *                 pseudo-root; a node's nucleotide mutations are applied to it in list order and undone
+ *                 after its subtree.  Block mutations are tracked (:294-333) and never read: the output
+ *                 does not depend on them, on which blocks a node holds or on strands, and nucleotide
+ *                 mutations of every block apply at every node.
+ *   entries       types 0 (NS), 1 (ND), 2 (NI) give info >> 4 elements, types 3, 4, 5 (NSNPS, NSNPI,
+ *                 NSNPD) one, types 6 and 7 none.  Element j's cell is (b, pos, gap + j) when gap != -1,
+ *                 else (b, pos + j, -1).  Per element, in order, one `mut`: position as above; ref_nuc =
+ *                 code(pseudo-root[cell]) with code = getCodeFromNucleotide (0 for '-' and 'x'); par_nuc
+ *                 = code of the RUNNING character at the cell (what an earlier element of the same list
+ *                 left there if any, else the parent's; the pseudo-root's for the root); mut_nuc = the
+ *                 ascending indices 0..3 of the set bits of c, c being the element's code for
+ *                 substitutions and insertions (a code of 0 counts as 15: get_nuc(0) is 'N') and 15 for
+ *                 both deletion types (newVal stays '-' there, :344, :432, :520, so deletions carry
+ *                 mut_nuc = {0, 1, 2, 3}; kept).  The running character becomes the code's character,
+ *                 '-' for a deletion.
+ *   bytes         proto3 as the Protobuf C++ library writes it: fields in number order, zero scalars
+ *                 left out, repeated int32 packed.  A mut is 08 varint(position) [10 ref] [18 par]
+ *                 22 len b0.., wrapped as 0a len body (chromosome is never set); a node is 12 varint(L)
+ *                 and its wrapped muts, L their bytes (an empty node: 12 00); the message is
+ *                 0a varint(len(newick)) newick and then the nodes.  The newick is Tree::getNewickString
+ *                 of the topology and branch lengths (defaults when `branch_length` is null), as the
+ *                 PanMAN writer prints it.
+ * `*mutations` (nullable) = the number of mut records.
+ * Deviations: a nucleotide mutation on a secondary block: PM_ERR_UNSUPPORTED, as pm_maf / pm_aa /
+ * pm_print_mutations (the reference would alias it onto the primary block); a mutation (types 0 to 5)
+ * whose cell does not exist: PM_ERR_ARG (the reference indexes out of bounds), on an id that holds no
+ * block or with a run longer than 6: PM_ERR_UNSUPPORTED, all from the replay; a duplicate primary block
+ * id: PM_ERR_UNSUPPORTED (the reference would append the second block's cells to the first's); rows of
+ * 2^31 - 64 columns and more, 2^31 - 64 nucleotide mutations and more, or a node whose list takes 2^31
+ * bytes and more: PM_ERR_UNSUPPORTED; condensed_nodes and metadata are not written (nor by the
+ * reference); no gzip.  Every refusal happens before the first byte reaches the sink or `fd`; only a
+ * failed write or a device failure can leave a partial output there.
+ * The rows of all nodes come from one replay of a derived PanMAT: that of pm_aa with the block mutations
+ * replaced by one plain insertion of every block at the root, so row v is the reference's running
+ * sequence after node v; the replay's consensus row is the pseudo-root.  The expansion of the lists into
+ * one entry per base, the column, ref and par lookups, the earlier writers of a cell within a list (a
+ * stable radix sort of (node, column) keys, each element reading its sorted predecessor), the sizes and
+ * the bytes are computed on the GPU (profiling class 3), batch by batch of nodes in pre-order
+ * (PM_OPT_USHER_BATCH_BYTES), the bytes streamed through the pinned download slots; the host writes the
+ * newick field.  Phase log: usher.*.  Memory: the replayed rows are nodes x columns bytes.
+ * `*bytes` is malloc'd (release with pm_free; `*length` bytes, NULs included, and one NUL after them);
+ * pm_to_usher_fd writes to `fd` instead (`length`, `mutations` nullable).  A failed write: PM_ERR_ARG
+ * (errno kept), as pm_fasta_fd. */
+int pm_to_usher(pm_ctx* ctx, const pm_panmat* panmat, char** bytes, int64_t* length, int64_t* mutations);
+int pm_to_usher_fd(pm_ctx* ctx, const pm_panmat* panmat, int fd, int64_t* length, int64_t* mutations);
 /* Canonical aligned columns per leaf of the prepared PanMAT (gap slots before each main
  * position, block sentinels included) and the number of leaves. */
 int pm_replay_shape(pm_ctx* ctx, int64_t* leaves, int64_t* columns, int64_t* edits);

@@ -1,7 +1,7 @@
 // panmanUtils-compatible command line for the GPU path (src/panmanUtils.cpp:128-182 option
 // table, :1302-1325 PanMAN load, :1409-1465 MSA build, :1326-1362 GFA build, :271-299 writePanMAN, :385-415 and
 // :458-490 FASTA / aligned FASTA, :584-652 subnetwork extraction, :699-732 GFA, :741-763 MAF, :766-786 Newick,
-// :895-938 amino-acid translation).  Only the commands on the accelerated
+// :895-938 amino-acid translation, :1008-1071 mutation printing, :1205-1240 UShER MAT export).  Only the commands on the accelerated
 // path are implemented; any other reference command is rejected with a message.
 #include <fcntl.h>
 #include <unistd.h>
@@ -59,6 +59,7 @@ const Spec kSpecs[] = {
     {"input-file", 'i', true, "Path to the input file, required for --subnet (one line per tree: treeID id id ...)"},
     {"reroot", 'r', false, "Reroot a PanMAT in a PanMAN based on the input sequence id (--reference)"},
     {"printMutations", 'p', false, "Print mutations from root to each node (every node of the tree given by --treeID, default 0)"},
+    {"toUsher", 0, false, "Convert a PanMAT in a PanMAN to an UShER MAT (needs --output-file, the file's name as given, and --reference; --treeID, default 0)"},
     {"aa-translation", 0, false, "Extract amino acid translations in TSV file (needs --treeID, --start and --end)"},
     {"start", 'x', true, "Start coordinate of protein translation"},
     {"end", 'y', true, "End coordinate of protein translation"},
@@ -76,8 +77,7 @@ const Spec kSpecs[] = {
 // Reference commands outside the accelerated path: recognised so the error is explicit.
 const char* const kOther[] = {"impute", "create-network", "printTips",
                               "vcf", "annotate",
-                              "extended-newick", "acr", "index",
-                              "toUsher"};
+                              "extended-newick", "acr", "index"};
 
 void usage(std::ostream& os) {
     os << "Allowed options:\n";
@@ -405,6 +405,58 @@ int print_mutations(const Options& o, const pm_panman* file, int device) {
     return one_tree_text(o, file, device, ".mutations", print_mutations_fd, "\nMutation extract execution time: ");
 }
 
+// -I in.panman --toUsher -o NAME -n REF [--treeID k] (src/panmanUtils.cpp:1205-1240): panmanToUsher of
+// one tree into the file NAME exactly as given -- no ./info/ prefix and no extension, as in the
+// reference (pm_to_usher_fd).  -n is required as there, though panmanToUsher never reads it.  The
+// reference converts every tree into the same file, so the last one survives; here the tree is
+// --treeID, default 0.  A missing -o or -n prints the reference's message and ends with status 1 (the
+// reference returns silently with status 0).  A NAME containing ".gz" is refused: the reference
+// gzips such a file, this build links no gzip.
+int to_usher(const Options& o, const pm_panman* file, int device) {
+    if (!o.has("output-file")) {
+        std::cout << "Output File not provided" << std::endl;
+        return 1;
+    }
+    if (!o.has("reference")) {
+        std::cout << "Reference not provided" << std::endl;
+        return 1;
+    }
+    const std::string p = o.get("output-file");
+    if (p.find(".gz") != std::string::npos) {
+        print_error("--toUsher: gzip output (a name containing .gz) is not built; give a plain name and compress the file");
+        return 1;
+    }
+    const int tree_id = o.has("treeID") ? std::atoi(o.get("treeID").c_str()) : 0;
+    if (tree_id < 0 || tree_id >= pm_panman_tree_count(file)) {
+        print_error("TreeID out of range");
+        return 1;
+    }
+    pm_ctx* ctx = nullptr;
+    if (pm_create(device, &ctx) != PM_OK) {
+        print_error("no HIP device");
+        return 1;
+    }
+    const int fd = ::open(p.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (fd < 0) {
+        print_error("cannot write " + p);
+        pm_destroy(ctx);
+        return 1;
+    }
+    int status = 0;
+    pm_panmat view;
+    int64_t len = 0;
+    const auto t0 = Clock::now();
+    if (pm_panman_tree(file, tree_id, &view) != PM_OK || pm_to_usher_fd(ctx, &view, fd, &len, nullptr) != PM_OK) {
+        print_error(pm_last_error(ctx));
+        status = 1;
+    }
+    const long long t = ns_since(t0);
+    if (::close(fd) != 0) status = 1;
+    pm_destroy(ctx);
+    if (status == 0) std::cout << "\nUsher Conversion time: " << t << " nanoseconds\n";
+    return status;
+}
+
 // -I in.panman --aa-translation --treeID k -x start -y end [-o out] (src/panmanUtils.cpp:895-938):
 // Tree::extractAminoAcidTranslations of one tree to stdout or ./info/<out>.tsv (pm_aa / pm_aa_fd).
 // stdout receives the reference's "<n> <n> <n>" line (the sizes of the root's three codon lists)
@@ -659,6 +711,11 @@ int from_panman(const Options& o, const std::vector<int>& devices) {
     }
     if (o.has("printMutations")) {
         status = print_mutations(o, file, device);
+        pm_panman_free(file);
+        return status;
+    }
+    if (o.has("toUsher")) {
+        status = to_usher(o, file, device);
         pm_panman_free(file);
         return status;
     }

@@ -1,9 +1,10 @@
 // pm_every_node.h -- the rows of every node, internal ones included, for the drivers that read
-// them (pm_aa, pm_mutations): the replay produces leaf rows, so they replay a derived PanMAT in
+// them (pm_aa, pm_mutations, pm_usher): the replay produces leaf rows, so they replay a derived PanMAT in
 // which every internal node has one more, childless child without mutations -- that child's row
 // is the internal node's row, and no replay kernel changes.  Also the columns' positions.
 #pragma once
 
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -12,14 +13,18 @@
 namespace pm {
 
 // `p` with a childless, mutation-free child under every internal node (ids num_nodes, ... in
-// the order of their parents); its arrays live in the object.
+// the order of their parents); its arrays live in the object.  With `every_block_at_root` the block
+// mutations of `p` are replaced by one plain insertion of every block at the root: every node then
+// holds every block forward, and every nucleotide mutation of its path applies (pm_usher).
 struct EveryNodeATip {
     pm_panmat q;
     std::vector<int32_t> child_offsets, child_index, tip_of;   // tip_of[v]: the leaf whose row is v's
     std::vector<int64_t> block_mut_offsets, nuc_mut_offsets;
     std::vector<char> names;
+    std::vector<int32_t> block_mut_primary;
+    std::vector<uint8_t> block_mut_info, block_mut_inversion;
 
-    explicit EveryNodeATip(const pm_panmat* p) : q(*p) {
+    explicit EveryNodeATip(const pm_panmat* p, bool every_block_at_root = false) : q(*p) {
         const int32_t N = p->num_nodes;
         tip_of.resize(N);
         int32_t extra = 0;
@@ -35,8 +40,20 @@ struct EveryNodeATip {
             child_offsets.push_back((int32_t)child_index.size());
         }
         child_offsets.insert(child_offsets.end(), (size_t)extra, child_offsets.back());
-        block_mut_offsets.assign(p->block_mut_offsets, p->block_mut_offsets + N + 1);
-        block_mut_offsets.insert(block_mut_offsets.end(), (size_t)extra, block_mut_offsets.back());
+        if (every_block_at_root) {
+            const int32_t B = std::max(p->num_blocks, 0);
+            block_mut_primary.assign(p->block_primary, p->block_primary + B);
+            block_mut_info.assign((size_t)B, 1);
+            block_mut_inversion.assign((size_t)B, 0);
+            block_mut_offsets.assign((size_t)N + 1 + extra, B);
+            std::fill(block_mut_offsets.begin(), block_mut_offsets.begin() + p->root + 1, 0);
+            q.block_mut_primary = block_mut_primary.data();
+            q.block_mut_info = block_mut_info.data();
+            q.block_mut_inversion = block_mut_inversion.data();
+        } else {
+            block_mut_offsets.assign(p->block_mut_offsets, p->block_mut_offsets + N + 1);
+            block_mut_offsets.insert(block_mut_offsets.end(), (size_t)extra, block_mut_offsets.back());
+        }
         nuc_mut_offsets.assign(p->nuc_mut_offsets, p->nuc_mut_offsets + N + 1);
         nuc_mut_offsets.insert(nuc_mut_offsets.end(), (size_t)extra, nuc_mut_offsets.back());
         q.num_nodes = N + extra;
@@ -74,6 +91,23 @@ inline void column_positions(const ReplayState& r, std::vector<int32_t>& col_mai
                 col_main[(size_t)col] = (int32_t)mc[j];
                 col_first[(size_t)col] = (int32_t)r.gap_col[id][j];
             }
+    });
+}
+
+// A cell (block, position, slot) as a column: main_col / gap_col[pos_off[block] + position] are the
+// columns of the position's main character and of its first gap slot (a block's positions 0..n_b).
+inline void cell_columns(const ReplayState& r, std::vector<int64_t>& pos_off, std::vector<int32_t>& main_col, std::vector<int32_t>& gap_col) {
+    const int32_t M = r.max_id + 1;
+    pos_off.assign((size_t)M + 1, 0);
+    for (int32_t id = 0; id < M; ++id) pos_off[(size_t)id + 1] = pos_off[(size_t)id] + (int64_t)r.main_col[id].size();
+    main_col.resize((size_t)pos_off[(size_t)M]);
+    gap_col.resize((size_t)pos_off[(size_t)M]);
+    host_parallel_for(M, [&](int id) {
+        if (!r.is_block[id]) return;
+        for (size_t j = 0; j < r.main_col[id].size(); ++j) {
+            main_col[(size_t)pos_off[(size_t)id] + j] = (int32_t)r.main_col[id][j];
+            gap_col[(size_t)pos_off[(size_t)id] + j] = (int32_t)r.gap_col[id][j];
+        }
     });
 }
 

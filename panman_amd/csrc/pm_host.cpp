@@ -463,7 +463,7 @@ int pm_warmup(int device) {
     if (e != hipSuccess || n == 0) return PM_ERR_HIP;
     if (device < 0 || device >= n) return PM_ERR_ARG;
     if ((e = hipSetDevice(device)) != hipSuccess) return PM_ERR_HIP;
-    for (auto warm : {warm_fitch, warm_sankoff, warm_fitch_nt, warm_sankoff_nt, warm_replay, warm_synth, warm_sort, warm_scan, warm_vcf, warm_maf, warm_gfa, warm_subnet, warm_aa, warm_mutations})
+    for (auto warm : {warm_fitch, warm_sankoff, warm_fitch_nt, warm_sankoff_nt, warm_replay, warm_synth, warm_sort, warm_scan, warm_vcf, warm_maf, warm_gfa, warm_subnet, warm_aa, warm_mutations, warm_usher})
         if ((e = warm()) != hipSuccess) return PM_ERR_HIP;
     // the runtime's first allocation and staged copies
     void* d = nullptr;
@@ -571,6 +571,11 @@ int pm_set_option(pm_ctx* c, int option, int64_t value) {
     if (option == PM_OPT_MUTATIONS_BATCH_BYTES) {
         if (value < 4096) return fail(c, PM_ERR_ARG, "PM_OPT_MUTATIONS_BATCH_BYTES: at least 4096");
         c->mutations_batch_bytes = value;
+        return PM_OK;
+    }
+    if (option == PM_OPT_USHER_BATCH_BYTES) {
+        if (value < 4096) return fail(c, PM_ERR_ARG, "PM_OPT_USHER_BATCH_BYTES: at least 4096");
+        c->usher_batch_bytes = value;
         return PM_OK;
     }
     if (option == PM_OPT_GFA_IN_BATCH_SITES) {

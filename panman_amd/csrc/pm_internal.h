@@ -228,6 +228,7 @@ struct pm_ctx {
     int64_t gfa_in_batch_sites = pm::kMaxUploadSites; // pm_gfa_build: block columns per upload and run (PM_OPT_GFA_IN_BATCH_SITES)
     int64_t aa_batch_bytes = (int64_t)1 << 30;    // pm_aa: codon tables and text per device batch of nodes (PM_OPT_AA_BATCH_BYTES)
     int64_t mutations_batch_bytes = (int64_t)1 << 30;   // pm_print_mutations: entry records and text per device batch of nodes (PM_OPT_MUTATIONS_BATCH_BYTES)
+    int64_t usher_batch_bytes = (int64_t)1 << 30;   // pm_to_usher: entry records, sort keys and bytes per device batch of nodes (PM_OPT_USHER_BATCH_BYTES)
     int64_t subnet_batch_entries = pm::kSubnetBatchEntries;   // pm_subnet: expanded bases sorted per batch (PM_OPT_SUBNET_BATCH_ENTRIES)
     int64_t reroot_chunk_sites = 0;               // pm_reroot: canonical columns per Fitch chunk, 0 = by the tree's size (PM_OPT_REROOT_CHUNK_SITES)
 };
@@ -737,6 +738,60 @@ hipError_t launch_mut_classify(pm_ctx* c, const MutArgs& a, const MutBatch& b);
 hipError_t launch_mut_line_len(pm_ctx* c, const MutArgs& a, const MutBatch& b);
 hipError_t launch_mut_write(pm_ctx* c, const MutArgs& a, const MutBatch& b);
 hipError_t warm_mutations();
+// UShER MAT export (pm_usher.hip; panmanToUsher, src/panman2usher.cpp:564-604) over the replayed rows
+// of every node, every block held forward at every node.  Nodes are addressed by pre-order rank; the
+// tree's nucleotide mutations are in rank order, list order within a node.
+constexpr int32_t kUsherRound = 256;     // entries per round of k_usher_write's workgroup
+constexpr int32_t kUsherMutBytes = 18;   // the most bytes of a wrapped `mut`: 0a len 08 p(5) 10 r 18 p 22 n b(4)
+struct UsherEntry {                // one element of a nucleotide mutation: one Parsimony::mut
+    int32_t position;              // 1 + the cells before it
+    uint8_t ref, par;              // 4-bit codes, 0 for '-' and 'x'
+    uint8_t set;                   // bit k: mut_nuc holds k (15 for a deletion and for code 0)
+    uint8_t after;                 // the code of the running character the element leaves (0: '-')
+};
+static_assert(sizeof(UsherEntry) == 8, "UsherEntry is 8 bytes");
+struct UsherArgs {
+    const char* rows;
+    int64_t row_stride, columns;
+    const char* pseudo;            // [columns] the pseudo-root row: consensus, '-' in gap slots, 'x' at sentinels
+    int32_t blocks;                // ids 0..max_id
+    const int64_t* pos_off;        // [blocks + 1] into main_col / gap_col (a block's positions 0..n_b)
+    const int32_t* main_col;
+    const int32_t* gap_col;
+    const int64_t* blk_lo;         // [blocks] the block's first column
+    const int64_t* cell_base;      // [blocks] the cells of the blocks of smaller id
+    const int32_t* par_row;        // [ranks] the replayed row of the rank's parent; -1 (the root): the pseudo-root row
+    const int64_t* rank_mut;       // [ranks + 1] the mutations of a rank
+    const int32_t* mut_rank;       // [mutations]
+    const int32_t* mut_primary;
+    const int32_t* mut_position;
+    const int32_t* mut_gap;
+    const uint8_t* mut_info;
+    const uint32_t* mut_nucs;
+    int32_t* error;                // [1] set when a mutation's cell does not exist
+};
+// One batch: the mutations [m0, m0 + m) of ranks [r0, r0 + n).
+struct UsherBatch {
+    int64_t m0, m, entries;
+    int32_t r0, n;
+    int64_t* elems;                // [m + 1] elements per mutation (the last 0); then the exclusive scan
+    UsherEntry* entry;             // [entries]
+    uint64_t* key;                 // [entries] (rank - r0) << 32 | column, and its double buffer
+    uint64_t* key_alt;
+    uint32_t* val;                 // [entries] the element's index, and its double buffer
+    uint32_t* val_alt;
+    uint32_t* list_len;            // [n] L: the bytes of the node's wrapped muts
+    int64_t* node_off;             // [n + 1] 1 + varint_len(L) + L (the last 0); then the scan
+    char* out;
+};
+hipError_t launch_usher_count(pm_ctx* c, const UsherArgs& a, const UsherBatch& b);
+hipError_t launch_usher_classify(pm_ctx* c, const UsherArgs& a, const UsherBatch& b);
+// An element whose cell an earlier element of its node's list wrote takes that element's `after`
+// as `par`: a stable sort of (key, val) and one look at the sorted predecessor.
+hipError_t usher_earlier_writers(pm_ctx* c, const UsherBatch& b);
+hipError_t launch_usher_sizes(pm_ctx* c, const UsherArgs& a, const UsherBatch& b);
+hipError_t launch_usher_write(pm_ctx* c, const UsherArgs& a, const UsherBatch& b);
+hipError_t warm_usher();
 // rows[leaf][c0 .. c0+n) chars -> packed codes out[leaf][(n+1)/2] ('-', 'x' -> 0)
 hipError_t launch_rows_to_codes(pm_ctx* c, const char* rows, int64_t row_stride, int32_t leaves, int64_t c0,
                                 int64_t n, uint8_t* out, int64_t out_stride);

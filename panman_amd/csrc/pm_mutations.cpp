@@ -82,16 +82,12 @@ int mutations_steps(pm_ctx* c, const pm_panmat* p, const Sink& sink, int64_t* le
             if (r.is_block[id] && held[(size_t)v * M + id] == 0)
                 return fail(c, PM_ERR_UNSUPPORTED, "a node ends its path with a block it does not hold flagged reverse");
     const std::vector<int32_t> row_of = every.rows_of_nodes(r, N);
-    std::vector<int64_t> pos_off((size_t)M + 1, 0);
-    for (int32_t id = 0; id < M; ++id) pos_off[(size_t)id + 1] = pos_off[(size_t)id] + (int64_t)r.main_col[id].size();
-    std::vector<int32_t> main_col((size_t)pos_off[(size_t)M]), gap_col((size_t)pos_off[(size_t)M]);
+    std::vector<int64_t> pos_off;
+    std::vector<int32_t> main_col, gap_col;
+    cell_columns(r, pos_off, main_col, gap_col);
     std::vector<uint8_t> col_held((size_t)r.columns, 0);
     host_parallel_for(M, [&](int id) {
         if (!r.is_block[id]) return;
-        for (size_t j = 0; j < r.main_col[id].size(); ++j) {
-            main_col[(size_t)pos_off[(size_t)id] + j] = (int32_t)r.main_col[id][j];
-            gap_col[(size_t)pos_off[(size_t)id] + j] = (int32_t)r.gap_col[id][j];
-        }
         if (held[(size_t)p->root * M + id] & kMafHeld)
             std::fill(col_held.begin() + r.col_start[id], col_held.begin() + r.col_start[id] + r.width[id], (uint8_t)1);
     });

@@ -18,6 +18,7 @@
 //                    at their scanned offsets, kMutRound entries a round with a carry
 // Integer only; only vector stores.
 #include "pm_bits.h"
+#include "pm_cell.h"
 #include "pm_dev.h"
 
 namespace pm {
@@ -71,28 +72,13 @@ __global__ __launch_bounds__(256) void k_mut_count(MutArgs a, MutBatch b) {
 __global__ __launch_bounds__(256) void k_mut_classify(MutArgs a, MutBatch b) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= b.entries) return;
-    // the mutation: the last k with elems[k] <= e (elems[m] = entries > e)
-    int64_t lo = 0, hi = b.m;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (b.elems[mid + 1] <= e) lo = mid + 1;
-        else hi = mid;
-    }
+    const int64_t lo = mutation_of_element(b.elems, b.m, e);
     const int32_t j = (int32_t)(e - b.elems[lo]);
     const int64_t g = b.m0 + lo;
     const int32_t blk = a.mut_primary[g], pos = a.mut_position[g], gap = a.mut_gap[g];
     const uint32_t info = a.mut_info[g], type = info & 7u;
     MutEntry out{0, 0, '-', '-', 0};
-    // the cell's column
-    int64_t col = -1;
-    if (blk >= 0 && blk < a.blocks && pos >= 0 && gap >= -1) {
-        const int64_t o = a.pos_off[blk], n = a.pos_off[blk + 1] - o;
-        if (gap != -1) {
-            if (pos < n && gap + j < a.main_col[o + pos] - a.gap_col[o + pos]) col = (int64_t)a.gap_col[o + pos] + gap + j;
-        } else if ((int64_t)pos + j < n) {
-            col = a.main_col[o + pos + j];
-        }
-    }
+    const int64_t col = cell_column(a.pos_off, a.main_col, a.gap_col, a.blocks, blk, pos, gap, j);
     if (col < 0 || col >= a.columns) {
         atomicOr(a.error, 1);
         b.entry[e] = out;
