@@ -183,6 +183,10 @@ int pm_set_stream(pm_ctx* ctx, void* hip_stream);
  *                  pre-order into batches by the bytes of their entry records, sort keys and worst-case
  *                  output (a node above the limit runs alone) and stream the bytes batch by batch.  The
  *                  bytes do not depend on it.
+ *   PM_OPT_IMPUTE_BATCH_ENTRIES (default 2^25, 1 .. 2^31 - 2): pm_impute lays out, sorts and folds the path lists of
+ *                  whole (node, candidate) pairs of at most this many bases per batch (a pair whose path holds
+ *                  more gets a batch of its own), and sorts the cells of whole nodes' lists in batches of the
+ *                  same size.  The result does not depend on it.
  * (Option ids 1, 4, 5 and 11 -- subtree-region, heavy-path-chain and level-band schedules,
  * tail records overlapped with the pre-order levels -- were measured slower than, or no
  * faster than, the level kernels on MI355X and removed.) */
@@ -209,6 +213,7 @@ int pm_set_stream(pm_ctx* ctx, void* hip_stream);
 #define PM_OPT_MUTATIONS_BATCH_BYTES 26
 #define PM_OPT_REROOT_CHUNK_SITES 27
 #define PM_OPT_USHER_BATCH_BYTES 28
+#define PM_OPT_IMPUTE_BATCH_ENTRIES 29
 int pm_set_option(pm_ctx* ctx, int option, int64_t value);
 /* Accumulate per-kernel-class device time with HIP events (see pm_kernel_times). */
 int pm_set_profiling(pm_ctx* ctx, int enable);
@@ -798,6 +803,74 @@ int pm_reroot(pm_ctx* ctx, const pm_panmat* tree, const char* leaf, pm_panman** 
  * inversion after deletion, insertion after inversion): PM_ERR_ARG with the reference's message; blocks and gap
  * slots of 2^32 coordinates or more in all: PM_ERR_UNSUPPORTED. */
 int pm_subnet(pm_ctx* ctx, const pm_panmat* tree, const char* const* ids, int64_t num_ids, pm_panman** out);
+
+/* Tree::imputeNs(allowedIndelDistance) (src/impute.cpp:4-79; the --impute command, src/panmanUtils.cpp:328-354) up to
+ * and including the plan of moves.  THE PLAN IS NOT APPLIED: the moves (src/impute.cpp:46-70, moveNode :339-358) have
+ * no defined behaviour to match -- moveNode falls off the end of a bool function, its dummy parent copies block
+ * mutations the new parent keeps, newInternalNodeId() restarts at node_1 on a loaded file, and the moves run in the
+ * hash order of an unordered_map of strings -- so the tree that comes back has the input's topology.
+ *   `*out`   a one-tree pm_panman (release with pm_panman_free) equal to `tree` in topology, names, blocks, gaps,
+ *            per-node options and branch lengths; the nucleotide lists are the substitution-imputed ones.
+ *   `*plan`  malloc'd text (release with pm_free; `*plan_length` bytes and one NUL): one block per node whose
+ *            insertions hold an N (an attempt), in node-id order.  Head line
+ *              name \t runs-with-N \t candidates \t new-parent-name \t nucImprovement \t blockImprovement
+ *            (without a winner the last three fields are ". -1 0"); under a winner its bestNewMuts, the block
+ *            mutations as "name \t B \t block \t insertion \t inversion" in ascending block id (the reference's
+ *            order is its hash map's), then the NucMuts as "name \t N \t block \t position \t gap \t info \t
+ *            nucs as %06x", `name` being the node to move.
+ *   `*stats` (nullable) the counts the command prints.
+ * Substitution pass (:142-184, :205-225), every node but the root (the root's list is never visited, :98, its Ns
+ *   stay): an NS or NSNPS record with an N among its first length() codes is erased; an NS's other bases come back
+ *   in its place as single NSNPS records (NucMut(other, i), src/panman.hpp:233-248) at position + i when the gap
+ *   position is -1, else at gap position + i; the count is length() minus the bases put back.  Ns inside insertion
+ *   and deletion records stay.  (std::find erasing "the first equal record" gives the same lists as erasing each
+ *   such record in place; nothing is searched.)
+ * State.  originalNucs[v][cell] is the code of the character at `cell` just before v's list is applied (:161),
+ *   anything that is no nucleotide letter being 0: the consensus, the root's nucleotide mutations on the blocks the
+ *   root holds after its own block mutations (getSequenceFromReference, src/panman.cpp:4820-4835), and below the
+ *   root every nucleotide mutation of the path whether or not its block is held (:151-163 never looks).  One replay
+ *   of a derived PanMAT gives these rows; they are read at the parent.
+ * Insertion census (:147-183), from the lists as given: runs of insertion records merged by
+ *   IndelPosition::mergeIndels (src/panman.hpp:408-421) with its quirks -- only the last run is a merge target,
+ *   records of other types in between do not end a run, a run headed at gap -1 merges a record whose nucPosition
+ *   continues it whatever that record's gap position, a run headed in a gap slot compares gap positions without
+ *   comparing nucPosition -- each with its N count; two runs of one node with equal IndelPosition collapse to the
+ *   first.
+ * Candidates (findNearbyInsertions, :288-337): from node->parent, at every node first the node, then its children in
+ *   order (but where the walk came from), then its parent; every step passes allowedDistance - branchLength computed
+ *   in float and truncated toward zero to an int (0 - 0.5 is 0: the walk goes on) and stops only below 0;
+ *   `branch_length` NULL: all 0, the whole tree.  A node is a candidate when the first of the moving node's N-bearing
+ *   runs that it also holds is not all N there (:300-308).  That "first" is in the moving node's list order here and
+ *   in hash order in the reference; it matters only where a candidate holds two of them, one of them all N.
+ * Score (:264-283): the lists from candidate to node -- a node the path leaves upward gives its list inverted
+ *   (MutationList::invertMutations, src/panman.cpp:2374-2420: insertions become deletions of code 0, deletions
+ *   insertions of the originals, substitutions go back to the originals; block insertions become deletions and block
+ *   deletions insertions, whose strand stays false: convertToInsertion assigns its parameter to itself, so the
+ *   wasBlockInv state it is handed is never stored), a node it enters downward its list as it is, the node's own list
+ *   last, all substitution-imputed -- through consolidateNucMutations, the substitution pass again and
+ *   consolidateBlockMutations.  nucImprovement = the sum of length() over the node's list minus that over the new
+ *   list, blockImprovement = the difference of the block list sizes; a candidate wins with nucImprovement > best and
+ *   blockImprovement >= best, from (-1, 0), both ratcheting: among equals the first in walk order.
+ * The substitution pass, the test for a cell written twice, the originals, every pair's path lists, their fold and
+ * length, and the winners' regrouped and imputed lists are computed on the GPU (profiling class 3), pairs in batches
+ * (PM_OPT_IMPUTE_BATCH_ENTRIES); the census, the walk, the block tables (fillBlockLookupTables, :186-203, with the
+ * strand undo of :130-139 that never applied the inversion on the way down) and the block folds run on the host.  A
+ * tree without an N in any substitution or insertion below the root launches nothing after the replay.  Phase log:
+ * impute.*.  Replaces the ctx's replay state.  Memory: the replayed rows are nodes x columns bytes.
+ * Errors: a list that writes one cell twice: PM_ERR_UNSUPPORTED "a cell written twice in one list" (the reference's
+ * undo, :122-128, would restore the wrong character and corrupt every later sibling); a nucleotide mutation with
+ * secondaryBlockId != -1: PM_ERR_UNSUPPORTED "secondary blocks"; a deletion record that carries codes:
+ * PM_ERR_UNSUPPORTED (the walk would write them as characters, the rows hold '-'); a cell outside its block or gap
+ * slots, a length nibble above 6, a type above 5, an NSNP* record whose length is not 1: PM_ERR_ARG; a block sequence
+ * on which consolidateBlockMutations throws: PM_ERR_ARG with the reference's message. */
+typedef struct pm_impute_stats {
+    int64_t imputed_bases;     /* "Imputed k/k SNPs/MNPs to N": the sum of imputeSubstitution's returns          */
+    int64_t insertion_nodes;   /* nodes, the root excepted, with an insertion run holding an N (the attempts)    */
+    int64_t moves_found;       /* of those, the ones findInsertionImputationMove gives a new parent              */
+    int64_t pairs;             /* (node, candidate) pairs scored                                                 */
+} pm_impute_stats;
+int pm_impute(pm_ctx* ctx, const pm_panmat* tree, int32_t max_distance, pm_panman** out, char** plan, int64_t* plan_length,
+              pm_impute_stats* stats);
 
 /* Drop-in for Tree(pangraph.json, newick, FILE_TYPE::PANGRAPH, reference) (src/panman.cpp:
  * 820-1273; CLI -P/-N, src/panmanUtils.cpp:1364-1407): the PanGraph model

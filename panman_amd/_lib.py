@@ -36,6 +36,10 @@ class Summary(C.Structure):
                                           "block_duplications", "block_translocations")]
 
 
+class ImputeStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("imputed_bases", "insertion_nodes", "moves_found", "pairs")]
+
+
 class Tree(C.Structure):
     _fields_ = [("num_nodes", C.c_int32), ("root", C.c_int32),
                 ("child_offsets", C.c_void_p), ("child_index", C.c_void_p)]
@@ -110,6 +114,8 @@ _SIGS = {
     "pm_panman_write": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_int]),
     "pm_reroot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]),
     "pm_subnet": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_char_p), C.c_int64, C.POINTER(C.c_void_p)]),
+    "pm_impute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                            C.POINTER(C.c_int64), C.POINTER(ImputeStats)]),
     "pm_pangraph_build": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]),
     "pm_gfa_build": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]),
     "pm_comm_unique_id": (C.c_int, [C.c_void_p, C.c_int64]),

@@ -1,7 +1,8 @@
 // panmanUtils-compatible command line for the GPU path (src/panmanUtils.cpp:128-182 option
 // table, :1302-1325 PanMAN load, :1409-1465 MSA build, :1326-1362 GFA build, :271-299 writePanMAN, :385-415 and
 // :458-490 FASTA / aligned FASTA, :584-652 subnetwork extraction, :699-732 GFA, :741-763 MAF, :766-786 Newick,
-// :895-938 amino-acid translation, :1008-1071 mutation printing, :1205-1240 UShER MAT export).  Only the commands on the accelerated
+// :895-938 amino-acid translation, :1008-1071 mutation printing, :1205-1240 UShER MAT export,
+// :328-354 N imputation up to its plan of moves).  Only the commands on the accelerated
 // path are implemented; any other reference command is rejected with a message.
 #include <fcntl.h>
 #include <unistd.h>
@@ -57,6 +58,8 @@ const Spec kSpecs[] = {
     {"gfa", 'g', false, "Convert any PanMAT in a PanMAN to a GFA file"},
     {"subnet", 'b', false, "Extract subnet of given PanMAN to a new PanMAN file based on the list of nodes provided in the input-file"},
     {"input-file", 'i', true, "Path to the input file, required for --subnet (one line per tree: treeID id id ...)"},
+    {"impute", 0, false, "Create new PanMAN with the N substitutions imputed; the moves found for insertions to N are planned in ./info/<output-file>_<tree>.moves, not applied (needs --output-file)"},
+    {"max-insertion-impute-distance", 'D', true, "Maximum total branch length to move a node for insertion imputation [default 5]"},
     {"reroot", 'r', false, "Reroot a PanMAT in a PanMAN based on the input sequence id (--reference)"},
     {"printMutations", 'p', false, "Print mutations from root to each node (every node of the tree given by --treeID, default 0)"},
     {"toUsher", 0, false, "Convert a PanMAT in a PanMAN to an UShER MAT (needs --output-file, the file's name as given, and --reference; --treeID, default 0)"},
@@ -75,7 +78,7 @@ const Spec kSpecs[] = {
 };
 
 // Reference commands outside the accelerated path: recognised so the error is explicit.
-const char* const kOther[] = {"impute", "create-network", "printTips",
+const char* const kOther[] = {"create-network", "printTips",
                               "vcf", "annotate",
                               "extended-newick", "acr", "index"};
 
@@ -337,6 +340,83 @@ int subnet(const Options& o, const pm_panman* file, int device) {
             status = 1;
         } else {
             std::cout << "\nParallel Subnetwork Extract execution time: " << ns_since(t0) << " nanoseconds\n";
+        }
+    }
+    for (pm_panman* r : results) pm_panman_free(r);
+    pm_destroy(ctx);
+    return status;
+}
+
+// -I in.panman --impute [-D distance] -o out (src/panmanUtils.cpp:328-354): Tree::imputeNs of every tree up to the
+// plan of moves (pm_impute), written as ./panman/<out>.panman; tree i's plan goes to ./info/<out>_<i>.moves.
+int impute(const Options& o, const pm_panman* file, int device) {
+    if (!o.has("output-file")) {
+        print_error("Output file not provided!");
+        usage(std::cout);
+        return 1;
+    }
+    int distance = 5;
+    if (o.has("max-insertion-impute-distance")) {
+        char* end = nullptr;
+        const std::string& text = o.get("max-insertion-impute-distance");
+        const long long v = std::strtoll(text.c_str(), &end, 10);
+        if (text.empty() || *end || v < -2147483647LL || v > 2147483647LL) {
+            print_error("the argument ('" + text + "') for option '--max-insertion-impute-distance' is invalid");
+            return 1;
+        }
+        distance = (int)v;
+    }
+    pm_ctx* ctx = nullptr;
+    if (pm_create(device, &ctx) != PM_OK) {
+        print_error("no HIP device");
+        return 1;
+    }
+    const int trees = pm_panman_tree_count(file);
+    std::vector<pm_panman*> results(trees, nullptr);
+    std::vector<pm_panmat> views(trees);
+    std::vector<const pm_panmat*> list;
+    std::vector<std::string> plans(trees);
+    int status = 0;
+    const auto t0 = Clock::now();
+    for (int i = 0; i < trees && status == 0; ++i) {
+        pm_panmat view;
+        pm_impute_stats stats;
+        char* plan = nullptr;
+        int64_t length = 0;
+        if (pm_panman_tree(file, i, &view) != PM_OK ||
+            pm_impute(ctx, &view, distance, &results[i], &plan, &length, &stats) != PM_OK) {
+            print_error(pm_last_error(ctx));
+            status = 1;
+            break;
+        }
+        plans[i].assign(plan, (size_t)length);
+        pm_free(plan);
+        std::cout << "Imputed " << stats.imputed_bases << "/" << stats.imputed_bases << " SNPs/MNPs to N" << std::endl;
+        std::cout << "Moved 0/" << stats.insertion_nodes << " nodes with insertions to N (" << stats.moves_found
+                  << " moves found, not applied)" << std::endl;
+        pm_panman_tree(results[i], 0, &views[i]);
+        list.push_back(&views[i]);
+    }
+    if (status == 0) {
+        std::cout << "\nImputation time: " << ns_since(t0) << " nanoseconds\n";
+        ::mkdir("./panman", 0777);
+        ::mkdir("./info", 0777);
+        const std::string out = "./panman/" + o.get("output-file") + ".panman";
+        std::cout << "Writing PanMAN" << std::endl;
+        const auto w0 = Clock::now();
+        if (pm_panman_write(out.c_str(), list.data(), (int)list.size(), 1) != PM_OK) {
+            print_error("cannot write " + out);
+            status = 1;
+        }
+        std::cout << "\nNetwork Write execution time: " << ns_since(w0) << " nanoseconds\n";
+        for (int i = 0; i < trees && status == 0; ++i) {
+            const std::string p = "./info/" + o.get("output-file") + "_" + std::to_string(i) + ".moves";
+            std::ofstream f(p, std::ios::binary);
+            f.write(plans[i].data(), (std::streamsize)plans[i].size());
+            if (!f) {
+                print_error("cannot write " + p);
+                status = 1;
+            }
         }
     }
     for (pm_panman* r : results) pm_panman_free(r);
@@ -691,6 +771,11 @@ int from_panman(const Options& o, const std::vector<int>& devices) {
     int status = 0;
     if (o.has("reroot")) {   // src/panmanUtils.cpp:855-892, then writePanMAN
         status = reroot(o, file, device);
+        pm_panman_free(file);
+        return status;
+    }
+    if (o.has("impute")) {
+        status = impute(o, file, device);
         pm_panman_free(file);
         return status;
     }

@@ -463,7 +463,7 @@ int pm_warmup(int device) {
     if (e != hipSuccess || n == 0) return PM_ERR_HIP;
     if (device < 0 || device >= n) return PM_ERR_ARG;
     if ((e = hipSetDevice(device)) != hipSuccess) return PM_ERR_HIP;
-    for (auto warm : {warm_fitch, warm_sankoff, warm_fitch_nt, warm_sankoff_nt, warm_replay, warm_synth, warm_sort, warm_scan, warm_vcf, warm_maf, warm_gfa, warm_subnet, warm_aa, warm_mutations, warm_usher})
+    for (auto warm : {warm_fitch, warm_sankoff, warm_fitch_nt, warm_sankoff_nt, warm_replay, warm_synth, warm_sort, warm_scan, warm_vcf, warm_maf, warm_gfa, warm_subnet, warm_aa, warm_mutations, warm_usher, warm_impute})
         if ((e = warm()) != hipSuccess) return PM_ERR_HIP;
     // the runtime's first allocation and staged copies
     void* d = nullptr;
@@ -586,6 +586,11 @@ int pm_set_option(pm_ctx* c, int option, int64_t value) {
     if (option == PM_OPT_SUBNET_BATCH_ENTRIES) {
         if (value < 1 || value >= ((int64_t)1 << 31) - 1) return fail(c, PM_ERR_ARG, "PM_OPT_SUBNET_BATCH_ENTRIES: 1 .. 2^31 - 2 bases");
         c->subnet_batch_entries = value;
+        return PM_OK;
+    }
+    if (option == PM_OPT_IMPUTE_BATCH_ENTRIES) {
+        if (value < 1 || value >= ((int64_t)1 << 31) - 1) return fail(c, PM_ERR_ARG, "PM_OPT_IMPUTE_BATCH_ENTRIES: 1 .. 2^31 - 2 bases");
+        c->impute_batch_entries = value;
         return PM_OK;
     }
     if (option == PM_OPT_REROOT_CHUNK_SITES) {

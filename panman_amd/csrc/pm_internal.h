@@ -230,6 +230,7 @@ struct pm_ctx {
     int64_t mutations_batch_bytes = (int64_t)1 << 30;   // pm_print_mutations: entry records and text per device batch of nodes (PM_OPT_MUTATIONS_BATCH_BYTES)
     int64_t usher_batch_bytes = (int64_t)1 << 30;   // pm_to_usher: entry records, sort keys and bytes per device batch of nodes (PM_OPT_USHER_BATCH_BYTES)
     int64_t subnet_batch_entries = pm::kSubnetBatchEntries;   // pm_subnet: expanded bases sorted per batch (PM_OPT_SUBNET_BATCH_ENTRIES)
+    int64_t impute_batch_entries = pm::kSubnetBatchEntries;   // pm_impute: expanded bases of whole pairs sorted per batch (PM_OPT_IMPUTE_BATCH_ENTRIES)
     int64_t reroot_chunk_sites = 0;               // pm_reroot: canonical columns per Fitch chunk, 0 = by the tree's size (PM_OPT_REROOT_CHUNK_SITES)
 };
 
@@ -631,6 +632,68 @@ struct SubnetOut {
 };
 hipError_t launch_subnet_pack(pm_ctx* c, const SubnetLive& s, const SubnetOut& o);
 hipError_t warm_subnet();
+// The rank tables of SubnetArgs, indexed by primary block id (as the replay's block tables are), and the text
+// of a kSubnet* code (pm_subnet.cpp; pm_impute sorts the same coordinates).
+struct RankTables {
+    std::vector<int32_t> blk_len;
+    std::vector<uint32_t> block_base, pos_base;
+    std::vector<int64_t> pos_off;
+};
+int rank_tables(pm_ctx* c, const pm_panmat* p, RankTables& t);
+const char* coordinate_error(int32_t code);
+// N imputation (pm_impute.hip; Tree::imputeNs, src/impute.cpp) over nucleotide records in list order.
+struct ImputeRecs {
+    int64_t n;
+    const int32_t* node;           // [n] the record's node (launch_impute_steps' source: unread)
+    const int32_t* primary;
+    const int32_t* pos;
+    const int32_t* gap;            // -1: main position
+    const uint8_t* info;           // (length << 4) | type
+    const uint32_t* nucs;
+};
+struct ImputeRecsOut {
+    int32_t* node;                 // nullable
+    int32_t* primary;
+    int32_t* pos;
+    int32_t* gap;
+    uint8_t* info;
+    uint32_t* nucs;
+};
+// imputeSubstitution (src/impute.cpp:205-225) per record: off[r] = the records that take its place -- 0 for an
+// NSNPS of N, the non-N bases of an NS holding an N, else 1 -- (off: n + 1 entries, the last 0; launch_impute_pack
+// takes the exclusive scan) and *imputed += the bases dropped.  Records [keep0, keep1) are kept as they are.
+hipError_t launch_impute_count(pm_ctx* c, const ImputeRecs& in, int64_t keep0, int64_t keep1, int64_t* off,
+                               unsigned long long* imputed);
+hipError_t launch_impute_pack(pm_ctx* c, const ImputeRecs& in, int64_t keep0, int64_t keep1, const int64_t* off, const ImputeRecsOut& out);
+// originalNucs (src/impute.cpp:161): orig[r] = the codes under the record's bases in its node's parent's replayed
+// row, packed as nucs are (0 for the root's records, par_row -1).  *error is set when a cell does not exist.
+struct ImputeRows {
+    const char* rows;
+    int64_t row_stride, columns;
+    int32_t blocks;                // ids 0..max_id
+    const int64_t* pos_off;        // [blocks + 1] into main_col / gap_col (a block's positions 0..n_b)
+    const int32_t* main_col;
+    const int32_t* gap_col;
+    const int32_t* par_row;        // [nodes] the replayed row of the node's parent; -1: the root
+    int32_t* error;
+};
+hipError_t launch_impute_originals(pm_ctx* c, const ImputeRecs& in, const ImputeRows& rows, uint32_t* orig);
+// The lists of a batch's path steps back to back: step s is records [src0[s], src0[s] + dst_off[s + 1] - dst_off[s])
+// of `src`, written at dst_off[s] with node = pair[s]; an inverted step's records as MutationList::invertMutations
+// (src/panman.cpp:2374-2420) leaves them, the originals from `orig`.
+struct ImputeSteps {
+    int64_t steps, records;        // records = dst_off[steps]
+    const int64_t* dst_off;        // [steps + 1]
+    const int64_t* src0;           // [steps]
+    const uint8_t* inverted;       // [steps]
+    const int32_t* pair;           // [steps] the batch's pair index
+};
+hipError_t launch_impute_steps(pm_ctx* c, const ImputeSteps& s, const ImputeRecs& src, const uint32_t* orig, const ImputeRecsOut& dst);
+// sum[pair] += the pair's survivors that are not a substitution with code N (sum zeroed by the caller)
+hipError_t launch_impute_pair_sum(pm_ctx* c, const SubnetLive& live, unsigned long long* sum);
+// *error |= 1 when two neighbours of the sorted keys are equal: a cell written twice in one list
+hipError_t launch_impute_twice(pm_ctx* c, const uint64_t* key, int64_t n, int32_t* error);
+hipError_t warm_impute();
 // Amino-acid translation (pm_aa.hip; Tree::extractAminoAcidTranslations, src/aaTrans.cpp:185-304)
 // over the replayed rows of every node: node v's row is rows[row_of[v]].  A cell of the canonical
 // row is a column; col_main / col_first give the column of its position's main character and of the

@@ -29,12 +29,7 @@ struct NewTree {
     std::vector<int32_t> parent;
 };
 
-// The rank tables of SubnetArgs, indexed by primary block id (as the replay's block tables are).
-struct RankTables {
-    std::vector<int32_t> blk_len;
-    std::vector<uint32_t> block_base, pos_base;
-    std::vector<int64_t> pos_off;
-};
+}  // namespace
 
 int rank_tables(pm_ctx* c, const pm_panmat* p, RankTables& t) {
     int32_t max_id = -1;
@@ -100,6 +95,8 @@ const char* coordinate_error(int32_t code) {
         default: return "the sort did not keep equal keys in entry order";
     }
 }
+
+namespace {
 
 // consolidateBlockMutations over a chain's lists; false with the reference's message in `err`.
 bool fold_blocks(const pm_panmat* p, const int32_t* chain, size_t links, PanmanTree& out, std::string& err) {
